@@ -7,8 +7,14 @@ analog noise I_max=1nA, act_max=5, bf16, synthetic 4-bit-CIFAR-shaped data
 Single GPU:       python bench.py --steps 100 --warmup 20
 Multi-GPU (driver): python -m torch.distributed.run --nnodes=1
     --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
-Accuracy:         python bench.py --top1 30   (trains the flagship on the
-    learnable synthetic CIFAR and reports held-out top-1 in the JSON line)
+Accuracy:         python bench.py --full --top1 30   (trains the flagship on
+    the learnable synthetic CIFAR and reports held-out top-1 in the JSON line)
+Outputs:          python bench.py --dump-outputs DIR   (writes what the last
+    timed step computed as DIR/<name>.npy, to compare two builds)
+
+A plain run only sets up, warms up, times --steps steps and prints the
+result line. Everything that takes runs of its own (today: the --top1
+accuracy run) sits behind --full.
 
 Weak scaling: per-GPU batch is fixed (--batch), global batch = N * batch.
 Each timed step is a FULL training step on a FRESH batch sliced from a
@@ -56,9 +62,17 @@ def parse_args():
                    help="disable analog/weight noise (noise-free baseline)")
     p.add_argument("--no-augment", action="store_true",
                    help="skip the in-loop GPU crop/flip (flagship only)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (today: the --top1 accuracy run)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss, gradients, updated parameters "
+                        "and buffers) as DIR/<name>.npy")
     p.add_argument("--top1", type=int, default=0, metavar="EPOCHS",
-                   help="after the throughput run, train the flagship on the "
-                        "learnable synthetic CIFAR for EPOCHS epochs and "
+                   help="with --full: after the throughput run, train the "
+                        "flagship on the learnable synthetic CIFAR for "
+                        "EPOCHS epochs and "
                         "report held-out top-1 (the accuracy half of the "
                         "BASELINE metric)")
     p.add_argument("--graph", action="store_true", default=None,
@@ -67,6 +81,10 @@ def parse_args():
     p.add_argument("--no-graph", dest="graph", action="store_false")
     p.add_argument("--seed", type=int, default=42)
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.top1 > 0 and not args.full:
+        p.error("--top1 is part of the full run: add --full")
     if args.batch == 0:
         # throughput-optimal per-GPU batch on 288 GB HBM3E (weak scaling
         # keeps this fixed as N grows). Sweep-measured: flagship 8192 ->
@@ -208,6 +226,41 @@ def run_top1(bench, device, dtype, rank, distributed):
         if rank == 0:
             print("# top1 epoch %d: %.2f%%" % (epoch, acc), file=sys.stderr)
     return curve
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # whole dump stays well under 64 MB
+
+
+def dump_outputs(out_dir, loss, model):
+    """Write what the last timed step left behind -- the loss it returned,
+    the gradients it computed, the parameters and buffers it updated -- as
+    float32 (float64 for integer buffers) ``<name>.npy`` files. Arrays that
+    would overflow the byte budget are cut to a fixed seeded sample."""
+    import numpy as np
+
+    arrays = {"loss": loss.detach()}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p.detach()
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach()
+    for name, b in model.named_buffers():
+        arrays["buffer." + name] = b.detach()
+
+    total = sum(t.numel() * (4 if t.is_floating_point() else 8)
+                for t in arrays.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.RandomState(1234)
+    for name, t in arrays.items():
+        a = t.to("cpu", torch.float32 if t.is_floating_point()
+                 else torch.float64).contiguous().numpy().reshape(-1)
+        if keep < 1.0 and a.size > 1024:
+            idx = np.sort(rng.choice(a.size, int(a.size * keep),
+                                     replace=False))
+            a = a[idx]
+        else:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -366,7 +419,7 @@ def main():
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(bench.steps):
-        step(i + 1000)
+        last_loss = step(i + 1000).detach()
     if device.type == "cuda":
         torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -382,8 +435,11 @@ def main():
     ms_per_step = elapsed / bench.steps * 1000.0
     images_per_sec = n_gpus * bench.batch * bench.steps / elapsed
 
+    if bench.dump_outputs and rank == 0:
+        dump_outputs(bench.dump_outputs, last_loss, model)
+
     top1_curve = None
-    if bench.top1 > 0 and bench.model == "noisynet":
+    if bench.full and bench.top1 > 0 and bench.model == "noisynet":
         top1_curve = run_top1(bench, device, dtype, rank, distributed)
 
     if rank == 0:

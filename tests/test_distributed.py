@@ -7,9 +7,19 @@ import pytest
 import torch
 
 
+def _hide_gpus():
+    """These are CPU (gloo) tests with one rank per LOCAL_RANK: on a box
+    with fewer GPUs than ranks, rank r would ask for a device r that does
+    not exist. Called first thing in each spawned worker, before the HIP
+    runtime starts, so the worker sees no GPU at all."""
+    os.environ["HIP_VISIBLE_DEVICES"] = "-1"
+    os.environ["CUDA_VISIBLE_DEVICES"] = "-1"
+
+
 def _worker(rank, world_size, port, q, delay):
     os.environ["RANK"] = str(rank)
     os.environ["LOCAL_RANK"] = str(rank)
+    _hide_gpus()
     os.environ["WORLD_SIZE"] = str(world_size)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -74,6 +84,7 @@ def test_dataparallel_grad_allreduce_gloo(delay):
 def _bench_worker(rank, world_size, port, q):
     os.environ["RANK"] = str(rank)
     os.environ["LOCAL_RANK"] = str(rank)
+    _hide_gpus()
     os.environ["WORLD_SIZE"] = str(world_size)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -123,6 +134,7 @@ def test_bench_multiprocess_cpu(world_size):
 def _missing_grad_worker(rank, world_size, port, q, delay):
     os.environ["RANK"] = str(rank)
     os.environ["LOCAL_RANK"] = str(rank)
+    _hide_gpus()
     os.environ["WORLD_SIZE"] = str(world_size)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -195,6 +207,7 @@ def test_dataparallel_missing_grads_and_ws4(world_size, delay):
 def _accum_worker(rank, world_size, port, q):
     os.environ["RANK"] = str(rank)
     os.environ["LOCAL_RANK"] = str(rank)
+    _hide_gpus()
     os.environ["WORLD_SIZE"] = str(world_size)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -249,6 +262,7 @@ def test_dataparallel_grad_accumulation_no_sync():
 def _syncbn_worker(rank, world_size, port, q):
     os.environ["RANK"] = str(rank)
     os.environ["LOCAL_RANK"] = str(rank)
+    _hide_gpus()
     os.environ["WORLD_SIZE"] = str(world_size)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
