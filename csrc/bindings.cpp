@@ -84,6 +84,15 @@ std::vector<torch::Tensor> se_scale_bwd(torch::Tensor g, torch::Tensor x,
                                         torch::Tensor s, int64_t act);
 torch::Tensor act_bwd(torch::Tensor g, torch::Tensor x, int64_t act);
 
+// image_pipeline.hip
+torch::Tensor crop_resize_mirror_normalize(torch::Tensor arena,
+                                           torch::Tensor offsets,
+                                           torch::Tensor meta,
+                                           int64_t out_size,
+                                           std::vector<double> mean,
+                                           std::vector<double> std,
+                                           int64_t out_dtype);
+
 // percentile.hip
 torch::Tensor kth_percentile(torch::Tensor x, double pctl);
 
@@ -165,6 +174,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("avgpool_fwd", &avgpool_fwd);
   m.def("avgpool_bwd", &avgpool_bwd);
   m.def("kth_percentile", &kth_percentile);
+  m.def("crop_resize_mirror_normalize", &crop_resize_mirror_normalize);
   m.def("conv_fwd", &conv_fwd);
   m.def("conv_fwd_fused", &conv_fwd_fused);
   m.def("conv_dgrad", &conv_dgrad);

@@ -269,4 +269,16 @@ def build_main_parser():
     parser.add_argument('--bf16', dest='bf16', action='store_true')
     parser.add_argument('--synthetic_batches', type=int, default=50,
                         help='batches per epoch for the synthetic loader')
+    # image-folder ingestion (used when <--data>/train is a directory)
+    parser.add_argument('--image_size', type=int, default=224,
+                        help='side of the square network input')
+    parser.add_argument('--store_size', type=int, default=256,
+                        help='shorter side images are stored at (never '
+                             'upsampled)')
+    parser.add_argument('--store_device', default='auto',
+                        choices=['auto', 'cuda', 'host'],
+                        help='where the decoded uint8 arena lives')
+    parser.add_argument('--data_cache', default=None, metavar='DIR',
+                        help='directory for the decoded-arena cache')
+    _bool_pair(parser, 'imagenet_norm', False)
     return parser

@@ -1,8 +1,9 @@
 """ImageNet training driver (the `python main.py -a resnet18 ...` entrypoint).
 
 Reproduces the reference main.py flow: build_model with
-arch select + distributed wiring, DALI-style GPU-resident data (here: the
-synthetic ImageNet-shaped generator -- no datasets in this environment),
+arch select + distributed wiring, DALI-style GPU-resident data (an image
+folder under --data through image_pipeline.py, else the synthetic
+ImageNet-shaped generator),
 the step/cos/linear LR schedules with warmup, L1/L3 penalties, calibration
 stop at batch 5, post-step weight clamp/percentile clip, per-epoch validate
 + rank-0 checkpointing ({epoch, arch, state_dict, best_acc, optimizer}),
@@ -65,12 +66,55 @@ def build_model(args):
     return model, dp, device, distributed
 
 
+def setup_folder_data(args, device, dtype, rank, ws):
+    """Loaders over <--data>/train and <--data>/val image folders: decoded
+    once into a resident uint8 arena, then one fused HIP kernel per batch
+    (image_pipeline.py; replaces the reference's DALI pipelines)."""
+    from .. import image_pipeline as ip
+    workers = min(args.workers, 16)
+
+    def store(split):
+        cache = os.path.join(args.data_cache, split) \
+            if args.data_cache else None
+        return ip.ImageStore(os.path.join(args.data, split),
+                             store_size=args.store_size, device=device,
+                             workers=workers, cache=cache,
+                             store_device=args.store_device)
+
+    train_store = store('train')
+    if os.path.isdir(os.path.join(args.data, 'val')):
+        val_store = store('val')
+    else:
+        val_store = train_store
+        if rank == 0:
+            print('[data] %s has no val folder -> validating on the train '
+                  'images with centre crops' % args.data)
+    if rank == 0:
+        print('[data] %d train / %d val images, %d classes, %.1f MB arena '
+              'on %s' % (len(train_store), len(val_store),
+                         len(train_store.classes), train_store.nbytes / 1e6,
+                         train_store.store_device))
+    mean, std = (ip.IMAGENET_MEAN, ip.IMAGENET_STD) if args.imagenet_norm \
+        else ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+    common = dict(size=args.image_size, dtype=dtype, mean=mean, std=std,
+                  rank=rank, world_size=ws)
+    seed = 1234 if args.seed is None else args.seed
+    train_loader = ip.GPUImageLoader(train_store, args.batch_size, train=True,
+                                     seed=seed, **common)
+    val_loader = ip.GPUImageLoader(val_store, args.batch_size, train=False,
+                                   **common)
+    return train_loader, val_loader
+
+
 def setup_data(args, device):
-    """Synthetic ImageNet-shaped loaders, rank-sharded (the DALI stand-in)."""
+    """Image-folder loaders when <--data>/train exists, else synthetic
+    ImageNet-shaped loaders, rank-sharded (the DALI stand-in)."""
     rank = dist_mod.env_rank()
     ws = dist_mod.env_world_size()
     dtype = torch.bfloat16 if getattr(args, 'bf16', False) else (
         torch.float16 if args.fp16 else torch.float32)
+    if os.path.isdir(os.path.join(args.data, 'train')):
+        return setup_folder_data(args, device, dtype, rank, ws)
     train_loader = data_mod.SyntheticImageNet(
         args.batch_size, num_batches=args.synthetic_batches, device=device,
         dtype=dtype, seed=1234, rank=rank, world_size=ws)
@@ -136,6 +180,8 @@ def train(model, dp, args, train_loader, val_loader, optimizer, device,
     num_iter = len(train_loader)
     for epoch in range(start_epoch, args.epochs):
         model.train()
+        if hasattr(train_loader, 'set_epoch'):
+            train_loader.set_epoch(epoch)
         for i, (images, target) in enumerate(train_loader):
             utils.adjust_learning_rate(args, optimizer, epoch, i, num_iter)
             if images.is_cuda:

@@ -1187,3 +1187,146 @@ def se_scale(x, s, gate='sigmoid'):
     gate_fn = torch.sigmoid if gate == 'sigmoid' \
         else lambda t: F.hardsigmoid(t)
     return x * gate_fn(s)
+
+
+# ---------------------------------------------------------------------------
+# Image batch preparation: crop + antialiased resize + mirror + normalise
+# ---------------------------------------------------------------------------
+
+_CROP_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+
+def _host_int_array(t, dtype, what):
+    """Host numpy copy of an index tensor (device tensors are copied back;
+    the loaders pass host tensors so their loop never syncs)."""
+    import numpy as np
+    if isinstance(t, torch.Tensor):
+        want = torch.int64 if dtype == np.int64 else torch.int32
+        if t.dtype != want:
+            raise ValueError('%s must be %s, got %s' % (what, want, t.dtype))
+        return t.detach().cpu().numpy()
+    a = np.asarray(t)
+    if a.dtype != dtype:
+        raise ValueError('%s must be %s, got %s' % (what, dtype, a.dtype))
+    return a
+
+
+def check_crop_request(arena_numel, offsets, meta, out_size):
+    """Validate host copies of a crop request; raises ValueError.
+
+    An invalid request must never reach the GPU: every bound the kernel
+    relies on (box inside the image, window inside the virtual image, image
+    inside the arena) is checked here with numpy.
+    """
+    import numpy as np
+    S = int(out_size)
+    if S < 1:
+        raise ValueError('out_size must be >= 1, got %d' % S)
+    if offsets.ndim != 1:
+        raise ValueError('offsets must be 1-D')
+    if meta.ndim != 2 or meta.shape != (offsets.shape[0], 11):
+        raise ValueError('meta must be [B, 11] with B = len(offsets), got %s'
+                         % (tuple(meta.shape),))
+    if meta.shape[0] == 0:
+        return
+    m = meta.astype(np.int64)
+    H, W, x0, y0, bw, bh, oh, ow, oy, ox, flip = (m[:, i] for i in range(11))
+
+    def need(cond, msg):
+        if not bool(np.all(cond)):
+            bad = int(np.argmin(cond))
+            raise ValueError('crop request sample %d: %s (meta=%s)'
+                             % (bad, msg, meta[bad].tolist()))
+
+    need((H >= 1) & (W >= 1), 'image size must be >= 1')
+    need((bw >= 1) & (bh >= 1), 'box extent must be >= 1')
+    need((x0 >= 0) & (x0 + bw <= W), 'box leaves the image on x')
+    need((y0 >= 0) & (y0 + bh <= H), 'box leaves the image on y')
+    need((oh >= 1) & (ow >= 1), 'virtual size must be >= 1')
+    need((oy >= 0) & (oy + S <= oh), 'window leaves the virtual image on y')
+    need((ox >= 0) & (ox + S <= ow), 'window leaves the virtual image on x')
+    need((flip == 0) | (flip == 1), 'flip must be 0 or 1')
+    need((offsets >= 0) & (offsets + 3 * H * W <= int(arena_numel)),
+         'image leaves the arena')
+
+
+def upload_crop_request(offsets, meta, device, targets=None):
+    """One non-blocking upload of (offsets int64[B], meta int32[B, 11]) and,
+    for the loaders, the batch's int64 labels.
+
+    All of it lives in one freshly allocated pinned buffer (the caching host
+    allocator keeps it alive until the copy has run), viewed on the device
+    as the tensors the kernel takes.
+    """
+    B = int(offsets.shape[0])
+    nt = 0 if targets is None else B
+    host = torch.empty(2 * (B + nt) + 11 * B, dtype=torch.int32,
+                       pin_memory=True)
+    host[:2 * B].view(torch.int64).copy_(torch.from_numpy(offsets))
+    if nt:
+        host[2 * B:4 * B].view(torch.int64).copy_(torch.from_numpy(targets))
+    host[2 * (B + nt):].view(B, 11).copy_(torch.from_numpy(meta))
+    dev = host.to(device, non_blocking=True)
+    off_d = dev[:2 * B].view(torch.int64)
+    meta_d = dev[2 * (B + nt):].view(B, 11)
+    if nt:
+        return off_d, meta_d, dev[2 * B:4 * B].view(torch.int64)
+    return off_d, meta_d
+
+
+def crop_resize_mirror_normalize(arena, offsets, meta, out_size,
+                                 mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0),
+                                 out_dtype=torch.float32, host_copies=None):
+    """Crop, antialiased-bilinear resize, window, mirror, normalise and cast
+    a whole batch out of a packed uint8 arena -> [B, 3, S, S] channels_last.
+
+    ``offsets`` (int64[B]) and ``meta`` (int32[B, 11]: H, W, x0, y0, bw, bh,
+    oh, ow, oy, ox, flip) are validated on the host before anything is
+    launched (ValueError). Pass them as host tensors/arrays in a loop: they
+    are then uploaded with one non-blocking copy; device tensors are
+    accepted too but cost a copy back for the validation, unless
+    ``host_copies=(offsets, meta)`` hands over the numpy arrays they were
+    uploaded from.
+    """
+    import numpy as np
+    if not isinstance(arena, torch.Tensor) or arena.dtype != torch.uint8 \
+            or arena.dim() != 1:
+        raise ValueError('arena must be a 1-D uint8 tensor')
+    if out_dtype not in _CROP_DTYPES:
+        raise ValueError('out_dtype must be float32, bfloat16 or float16')
+    mean = tuple(float(v) for v in mean)
+    std = tuple(float(v) for v in std)
+    if len(mean) != 3 or len(std) != 3 or min(std) <= 0:
+        raise ValueError('mean/std need 3 values each, std > 0')
+    for name, t in (('offsets', offsets), ('meta', meta)):
+        if isinstance(t, torch.Tensor) and t.is_cuda and t.device != arena.device:
+            raise ValueError('%s is on %s but the arena is on %s'
+                             % (name, t.device, arena.device))
+    if host_copies is not None:
+        off_np = _host_int_array(host_copies[0], np.int64, 'offsets')
+        meta_np = _host_int_array(host_copies[1], np.int32, 'meta')
+        if off_np.shape[0] != offsets.shape[0] \
+                or tuple(meta.shape) != tuple(meta_np.shape):
+            raise ValueError('host_copies do not match offsets/meta')
+    else:
+        off_np = _host_int_array(offsets, np.int64, 'offsets')
+        meta_np = _host_int_array(meta, np.int32, 'meta')
+    check_crop_request(arena.numel(), off_np, meta_np, out_size)
+
+    if use_native(arena):
+        if isinstance(offsets, torch.Tensor) and offsets.is_cuda \
+                and isinstance(meta, torch.Tensor) and meta.is_cuda:
+            off_d, meta_d = offsets.contiguous(), meta.contiguous()
+        else:
+            off_d, meta_d = upload_crop_request(
+                np.ascontiguousarray(off_np), np.ascontiguousarray(meta_np),
+                arena.device)
+        return ext().crop_resize_mirror_normalize(
+            arena.contiguous(), off_d, meta_d, int(out_size), list(mean),
+            list(std), _CROP_DTYPES[out_dtype])
+    arena_h = arena.cpu() if arena.is_cuda else arena
+    out = ref.crop_resize_mirror_normalize(
+        arena_h, torch.from_numpy(off_np), torch.from_numpy(meta_np),
+        int(out_size), mean, std, out_dtype)
+    # NOISYNET_FORCE_REFERENCE with a GPU arena: hand the result back there
+    return out.to(arena.device) if arena.is_cuda else out

@@ -158,3 +158,39 @@ def maxpool2x2(x):
 
 def softmax_xent(logits, target):
     return F.cross_entropy(logits, target)
+
+
+# ---------------------------------------------------------------------------
+# Image batch preparation (crop -> antialiased resize -> window -> mirror ->
+# normalise), the oracle for csrc/image_pipeline.hip
+# ---------------------------------------------------------------------------
+
+
+def crop_resize_mirror_normalize(arena, offsets, meta, out_size, mean, std,
+                                 out_dtype=torch.float32):
+    """Per-sample ``F.interpolate(..., antialias=True)`` composition.
+
+    ``arena`` is 1-D uint8 (images packed HWC RGB), ``offsets`` int64[B],
+    ``meta`` int32[B, 11] = H, W, x0, y0, bw, bh, oh, ow, oy, ox, flip.
+    The box is resized to (oh, ow), the out_size window at (oy, ox) is taken,
+    mirrored on x when flip is set, then ``(v - mean) / std`` on the [0, 1]
+    values. Returns [B, 3, S, S] channels_last in ``out_dtype`` (replaces the
+    reference's DALI Resize + CropMirrorNormalize, utils.py:63-116).
+    """
+    S = int(out_size)
+    B = int(offsets.shape[0])
+    mean_t = torch.tensor(mean, dtype=torch.float32).view(3, 1, 1)
+    std_t = torch.tensor(std, dtype=torch.float32).view(3, 1, 1)
+    out = torch.empty((B, 3, S, S), dtype=torch.float32)
+    for b in range(B):
+        H, W, x0, y0, bw, bh, oh, ow, oy, ox, flip = (int(v) for v in meta[b])
+        off = int(offsets[b])
+        img = arena[off:off + 3 * H * W].view(H, W, 3)
+        box = img[y0:y0 + bh, x0:x0 + bw].permute(2, 0, 1).float() / 255.0
+        r = F.interpolate(box[None], size=(oh, ow), mode='bilinear',
+                          antialias=True, align_corners=False)[0]
+        r = r[:, oy:oy + S, ox:ox + S]
+        if flip:
+            r = r.flip(-1)
+        out[b] = (r - mean_t) / std_t
+    return out.to(out_dtype).contiguous(memory_format=torch.channels_last)
