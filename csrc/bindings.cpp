@@ -119,6 +119,20 @@ torch::Tensor conv_wgrad_im2col(torch::Tensor gy, torch::Tensor x,
 torch::Tensor conv_wgrad_patch(torch::Tensor gy, torch::Tensor x,
                                int64_t stride, int64_t pad, int64_t R,
                                int64_t S);
+
+// conv_pool_fused.hip
+bool conv_pool_eligible(int64_t C, int64_t H, int64_t W, int64_t K, int64_t R,
+                        int64_t S, int64_t elem_size);
+std::vector<torch::Tensor> conv_pool_fwd_fused(torch::Tensor x,
+                                               torch::Tensor wq,
+                                               torch::Tensor wraw,
+                                               torch::Tensor bias,
+                                               int64_t sigma_mode,
+                                               torch::Tensor factor,
+                                               int64_t seed);
+torch::Tensor conv_pool_wgrad(torch::Tensor gp, torch::Tensor code,
+                              torch::Tensor x, int64_t R, int64_t S);
+
 torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w);
 torch::Tensor linear_dgrad(torch::Tensor gy, torch::Tensor w);
 torch::Tensor linear_wgrad(torch::Tensor gy, torch::Tensor x);
@@ -182,6 +196,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_wgrad_im2col", &conv_wgrad_im2col);
   m.def("conv_wgrad_patch", &conv_wgrad_patch);
   m.def("conv_wgrad_from_col", &conv_wgrad_from_col);
+  m.def("conv_pool_eligible", &conv_pool_eligible);
+  m.def("conv_pool_fwd_fused", &conv_pool_fwd_fused);
+  m.def("conv_pool_wgrad", &conv_pool_wgrad);
   m.def("im2col_materialize", &im2col_materialize);
   m.def("linear_fwd", &linear_fwd);
   m.def("linear_dgrad", &linear_dgrad);

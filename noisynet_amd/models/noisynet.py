@@ -14,6 +14,16 @@ sampled in-kernel) and pool/BN/ReLU/clip run as fused epilogue kernels.
 The introspective path (plot/merge_bn/L2_act*/print_stats/train_act_max)
 falls back to the compositional ops to expose every intermediate the
 reference exposes (model.conv1_, model.relu1_, ...).
+
+conv1 + its max-pool: in steady state (telemetry off, i >= 20) with no
+double-backward penalty (L3/L3_new/L4 == 0) the hot path runs conv1, its
+noise and the 2x2 max-pool as ONE kernel (ops.fused_noisy_conv2d_pool: the
+im2col rows are gathered in-kernel, the pool happens in registers) and the
+backward as one un-pool + wgrad kernel. The forward is bit-identical to the
+two-op composition, so the switch at iteration 20 is invisible. On that path
+the un-pooled activation never exists and ``model.conv1_`` is None; only the
+introspective path and the L2_act/L3_act penalties read it, and those never
+take the fused-pool path. NOISYNET_NO_CONV1_POOL=1 selects the composition.
 """
 
 import torch
@@ -97,9 +107,18 @@ class Net(nn.Module):
                 or a.train_act_max or a.uniform_ind > 0 or a.uniform_dep > 0
                 or a.normal_ind > 0 or a.normal_dep > 0)
 
+    def _conv1_pool_fused(self, x, i):
+        """conv1 and its max-pool run as one kernel (see module docstring)."""
+        a = self.args
+        return (a.current1 > 0 and i >= 20 and not x.requires_grad
+                and a.L3 == 0 and a.L4 == 0
+                and getattr(a, 'L3_new', 0) == 0
+                and ops.conv_pool_eligible(x, self.conv1.weight))
+
     def _noisy_layer_fused(self, x, layer, current, merged_dac, i, layer_num,
-                           is_conv):
-        """One fused pass: quantized-weight conv/GEMM + sigma + noise."""
+                           is_conv, pool=False):
+        """One fused pass: quantized-weight conv/GEMM + sigma + noise
+        (+ the following 2x2 max-pool when ``pool``)."""
         a = self.args
         w_raw = layer.weight
         wq, bias = layer.effective_weight()
@@ -121,7 +140,9 @@ class Net(nn.Module):
                 power_denom = input_max
         telem = ops.NoiseTelemetry() if want_telemetry else None
         if is_conv:
-            out = ops.fused_noisy_conv2d(
+            conv = ops.fused_noisy_conv2d_pool if pool \
+                else ops.fused_noisy_conv2d
+            out = conv(
                 x, wq, w_raw.detach(), bias, 1, 0, sigma_mode, factor,
                 current=current, power_denom=power_denom,
                 want_telemetry=want_telemetry, telemetry_out=telem)
@@ -158,13 +179,18 @@ class Net(nn.Module):
         x = self.quantize1(input) if args.q_a1 > 0 else input
         self.input = x
 
-        if args.current1 > 0:
+        if self._conv1_pool_fused(x, i):
             x = self._noisy_layer_fused(x, self.conv1, args.current1,
-                                        args.merged_dac, i, 0, True)
+                                        args.merged_dac, i, 0, True, pool=True)
+            self.conv1_ = None
         else:
-            x = self.conv1(x)
-        self.conv1_ = x
-        x = ops.maxpool2x2(x)
+            if args.current1 > 0:
+                x = self._noisy_layer_fused(x, self.conv1, args.current1,
+                                            args.merged_dac, i, 0, True)
+            else:
+                x = self.conv1(x)
+            self.conv1_ = x
+            x = ops.maxpool2x2(x)
         if args.batchnorm:
             x = self._bn_act(x, self.bn1, args.act_max1)
         else:

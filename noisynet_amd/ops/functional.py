@@ -343,6 +343,81 @@ def fused_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode,
                                  telemetry_out, current, power_denom)
 
 
+# ---- noisy conv fused with its 2x2 max-pool (small-C image convs) ---------
+
+
+def conv_pool_eligible(x, w, stride=1, padding=0):
+    """Whether fused_noisy_conv2d_pool runs the single-kernel conv+pool pair:
+    native 16-bit tensors, stride 1, pad 0, R*S*C <= 128, K <= 96, even
+    OH/OW with OW % 4 == 0 (the csrc check adds the LDS-size limits)."""
+    if _os.environ.get("NOISYNET_NO_CONV1_POOL"):
+        return False
+    if not use_native(x, w) or stride != 1 or padding != 0:
+        return False
+    if x.dtype != w.dtype or x.dim() != 4:
+        return False
+    return bool(ext().conv_pool_eligible(
+        x.shape[1], x.shape[2], x.shape[3], w.shape[0], w.shape[2],
+        w.shape[3], x.element_size()))
+
+
+class _FusedNoisyConvPool(torch.autograd.Function):
+    """maxpool2x2(fused noisy conv) as ONE kernel each way.
+
+    Forward gathers the conv's im2col rows from the NHWC input in-kernel
+    and pools in registers: neither the im2col matrix nor the un-pooled
+    activation reaches memory, and the result (values and argmax code) is
+    bit-identical to ``maxpool2x2(fused_noisy_conv2d(...))`` under the same
+    seed. Backward is the weight gradient only (first-layer use: the input
+    needs no gradient), computed from the pooled gradient, the code and x.
+    Saves x, wq and the code -- not the im2col matrix.
+    """
+
+    @staticmethod
+    def forward(ctx, x, wq, w_raw, bias, sigma_mode, factor):
+        ctx.has_bias = bias is not None
+        y, code = ext().conv_pool_fwd_fused(
+            _nhwc(x), _nhwc(wq), _nhwc(w_raw),
+            bias if bias is not None
+            else torch.empty(0, device=x.device, dtype=x.dtype),
+            1 if sigma_mode == "abs" else 2,
+            _factor_tensor(factor, x.device), _next_seed(x.device))
+        ctx.save_for_backward(x, wq, code)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, wq, code = ctx.saved_tensors
+        gw = gb = None
+        if ctx.needs_input_grad[1]:
+            gw = ext().conv_pool_wgrad(_nhwc(g), code, _nhwc(x),
+                                       wq.shape[2], wq.shape[3])
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            # every pooled gradient lands on exactly one un-pooled cell
+            gb = g.sum(dim=(0, 2, 3))
+        return None, gw, None, gb, None, None
+
+
+def fused_noisy_conv2d_pool(x, wq, w_raw, bias, stride, padding, sigma_mode,
+                            factor, current=0.0, power_denom=1.0,
+                            want_telemetry=False, telemetry_out=None):
+    """``maxpool2x2(fused_noisy_conv2d(...))``; one fused kernel pair when
+    the layer is eligible (see conv_pool_eligible), the input needs no
+    gradient and no telemetry is wanted, else exactly that composition
+    (also the CPU/reference path). NOISYNET_NO_CONV1_POOL=1 forces the
+    composition."""
+    if (not want_telemetry and not x.requires_grad
+            and conv_pool_eligible(x, wq, stride, padding)):
+        return _FusedNoisyConvPool.apply(x, wq, w_raw, bias, sigma_mode,
+                                         factor)
+    y = fused_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode,
+                           factor, current=current, power_denom=power_denom,
+                           want_telemetry=want_telemetry,
+                           telemetry_out=telemetry_out)
+    return maxpool2x2(y)
+
+
 # ---- sigma-only variants (noise tensor alone; used by the standalone
 # add_noise_calculate_power API path where the clean output already exists) --
 
