@@ -154,6 +154,11 @@ std::vector<torch::Tensor> sigma_noise_linear_impl(torch::Tensor x,
                                                    int64_t seed,
                                                    bool telem);
 
+std::string conv_fused_route(int64_t C, int64_t H, int64_t W, int64_t K,
+                             int64_t R, int64_t S, int64_t stride, int64_t pad,
+                             int64_t elem_size);
+std::string linear_fused_route(int64_t Kc, int64_t K, int64_t elem_size);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fake_quant_fwd", &fake_quant_fwd);
   m.def("ste_mask", &ste_mask);
@@ -197,6 +202,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_wgrad_patch", &conv_wgrad_patch);
   m.def("conv_wgrad_from_col", &conv_wgrad_from_col);
   m.def("conv_pool_eligible", &conv_pool_eligible);
+  m.def("conv_fused_route", &conv_fused_route);
+  m.def("linear_fused_route", &linear_fused_route);
   m.def("conv_pool_fwd_fused", &conv_pool_fwd_fused);
   m.def("conv_pool_wgrad", &conv_pool_wgrad);
   m.def("im2col_materialize", &im2col_materialize);

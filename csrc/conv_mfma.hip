@@ -1246,6 +1246,8 @@ inline void check_cl(const torch::Tensor& t, const char* name) {
               name, ": expected 4-D channels_last tensor");
 }
 
+void check_sigma_mode(int64_t sigma_mode, bool allow_zero, const char* who);
+
 }  // namespace
 
 // ===========================================================================
@@ -1286,6 +1288,7 @@ std::vector<torch::Tensor> conv_fwd_fused_impl(torch::Tensor x,
                                                torch::Tensor factor,
                                                int64_t seed,
                                                bool telem, bool want_y) {
+  check_sigma_mode(sigma_mode, false, "conv_fwd_fused (streaming route)");
   check_cl(x, "conv_fwd_fused x");
   auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
                      (int)x.size(1), (int)wraw.size(0), (int)wraw.size(2),
@@ -1528,17 +1531,40 @@ torch::Tensor linear_wgrad(torch::Tensor gy, torch::Tensor x) {
 
 namespace {
 
-// host side of the small-K fused GEMM (see conv_fwd_smallk_kernel)
+// Route of the fused noisy GEMM out[M,K] = x[M,Kc] @ w[K,Kc]^T. The one
+// place the choice is made: linear_fwd_fused / sigma_noise_linear dispatch
+// on it and linear_fused_route reports it.
+enum class LinearRoute { SmallK, Gemm };
+
+LinearRoute linear_route(int64_t Kc, int64_t K, int64_t elem_size) {
+  // small-K kernel (see conv_fwd_smallk_kernel); Kc % 32 == 0: its A/W
+  // staging loads carry no column bounds checks
+  if (Kc <= 128 && (Kc & 31) == 0 && K <= 96 && elem_size == 2)
+    return LinearRoute::SmallK;
+  return LinearRoute::Gemm;
+}
+
 bool smallk_eligible(const torch::Tensor& x, int64_t K) {
-  // Kc % 32 == 0: the A/W staging loads carry no column bounds checks
-  return x.size(1) <= 128 && (x.size(1) & 31) == 0 && K <= 96 &&
-         x.element_size() == 2;
+  return linear_route(x.size(1), K, (int64_t)x.element_size()) ==
+         LinearRoute::SmallK;
+}
+
+// The fused kernels are instantiated for sigma_mode 1 (|w|) and 2
+// (|w|^2+|w|); a noise-free mode 0 exists only where allow_zero says so.
+// Anything else used to fall through to the mode-2 launch.
+void check_sigma_mode(int64_t sigma_mode, bool allow_zero, const char* who) {
+  TORCH_CHECK(sigma_mode == 1 || sigma_mode == 2 ||
+                  (allow_zero && sigma_mode == 0),
+              who, ": sigma_mode ", sigma_mode, " is not supported here (",
+              allow_zero ? "0, " : "", "1 or 2)");
 }
 
 std::vector<torch::Tensor> linear_fwd_fused_smallk(
     torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
     int64_t sigma_mode, torch::Tensor factor, int64_t seed, bool telem,
     bool want_y) {
+  // the noise-free S0 variant exists with the y accumulator only
+  check_sigma_mode(sigma_mode, want_y, "linear_fwd_fused_smallk");
   int64_t M = x.size(0);
   int K = (int)wraw.size(0);
   int Kc = (int)x.size(1);
@@ -1627,6 +1653,7 @@ std::vector<torch::Tensor> linear_fwd_fused(torch::Tensor x, torch::Tensor wq,
   if (smallk_eligible(x, wraw.size(0)))
     return linear_fwd_fused_smallk(x, wq, wraw, bias, sigma_mode, factor,
                                    seed, telem, /*want_y=*/true);
+  check_sigma_mode(sigma_mode, false, "linear_fwd_fused");
   auto g = linear_geom(x, wraw.size(0));
   // row-pad the (small) weight matrices to the 64-row k-tile multiple so
   // the staging guard k < Kw never diverges inside a tile (the masked
@@ -1700,6 +1727,7 @@ std::vector<torch::Tensor> sigma_noise_linear_impl(torch::Tensor x,
     return linear_fwd_fused_smallk(x, wraw, wraw, empty_bias, sigma_mode,
                                    factor, seed, telem, /*want_y=*/false);
   }
+  check_sigma_mode(sigma_mode, false, "sigma_noise_linear");
   auto g = linear_geom(x, wraw.size(0));
   auto out = torch::empty({x.size(0), (int64_t)g.K}, x.options());
   // telemetry buffer only when requested (steady-state training has
@@ -1747,6 +1775,11 @@ std::vector<torch::Tensor> sigma_noise_linear_impl(torch::Tensor x,
   });
   HIP_CHECK_LAST();
   return {out, tele};
+}
+
+std::string linear_fused_route(int64_t Kc, int64_t K, int64_t elem_size) {
+  return linear_route(Kc, K, elem_size) == LinearRoute::SmallK ? "smallk"
+                                                               : "gemm";
 }
 
 // ===========================================================================
@@ -2065,6 +2098,27 @@ inline bool patch_eligible(const ConvGeom& g, int elem_bytes) {
   return g.R * g.S > 1 && g.C > 8 && patch_bytes <= 96 * 1024;
 }
 
+// Route of the fused noisy conv. The one place the choice is made:
+// conv_fwd_fused / sigma_noise_conv dispatch on it and conv_fused_route
+// reports it. The two Col routes differ only in the GEMM that
+// linear_route picks for the im2col matrix.
+enum class ConvRoute { Patch, ColSmallK, ColGemm, Stream };
+
+// width of the flat im2col matrix (see im2col_materialize)
+inline int col_width(const ConvGeom& g) {
+  int rsc = g.R * g.S * g.C;
+  return ((g.C & 7) == 0) ? rsc : ((rsc + 31) & ~31);
+}
+
+inline ConvRoute conv_route(const ConvGeom& g, int elem_bytes) {
+  if (patch_eligible(g, elem_bytes)) return ConvRoute::Patch;
+  if (g.flat)
+    return linear_route(col_width(g), g.K, elem_bytes) == LinearRoute::SmallK
+               ? ConvRoute::ColSmallK
+               : ConvRoute::ColGemm;
+  return ConvRoute::Stream;
+}
+
 // pad the raw-[K,R,S,C] weight view to [K,R,S*C_pad] (tiny tensors)
 inline torch::Tensor pad_weight_raw(const torch::Tensor& w, int c_pad) {
   auto raw = w.permute({0, 2, 3, 1});  // logical [K,C,R,S] cl -> raw view
@@ -2095,6 +2149,8 @@ std::vector<torch::Tensor> conv_fwd_fused_patch_impl(
     torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
     int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
     int64_t seed, bool telem, bool want_y) {
+  // the noise-free S0 variant exists with the y accumulator only
+  check_sigma_mode(sigma_mode, want_y, "conv_fwd_fused (patch route)");
   check_cl(x, "conv_fwd_patch x");
   auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
                      (int)x.size(1), (int)wraw.size(0), (int)wraw.size(2),
@@ -2199,8 +2255,14 @@ std::vector<torch::Tensor> conv_fwd_fused_col_impl(
                      (int)x.size(1), (int)wraw.size(0), (int)wraw.size(2),
                      (int)wraw.size(3), (int)stride, (int)pad);
   int rsc = g.R * g.S * g.C;
-  int cols_p = ((g.C & 7) == 0) ? rsc : ((rsc + 31) & ~31);
+  int cols_p = col_width(g);
+  // checked here too, before the im2col pass is launched
+  check_sigma_mode(sigma_mode,
+                   want_y && linear_route(cols_p, g.K, (int64_t)x.element_size())
+                                 == LinearRoute::SmallK,
+                   "conv_fwd_fused (im2col route)");
   auto col = im2col_materialize(x, g.K, stride, pad, g.R, g.S);  // [M,cols_p]
+  TORCH_CHECK(col.size(1) == cols_p, "conv_fwd_fused: im2col width mismatch");
   // flat weight rows: raw [K,R,S,C] view reshaped to [K, R*S*C],
   // column-padded to match col (row padding to the 96-row LDS image
   // happens inside the small-K host so K stays the logical count)
@@ -2238,14 +2300,21 @@ std::vector<torch::Tensor> conv_fwd_fused(torch::Tensor x, torch::Tensor wq,
                      (int)x.size(1), (int)wraw.size(0), (int)wraw.size(2),
                      (int)wraw.size(3), (int)stride, (int)pad);
   auto empty = torch::empty({0}, x.options());
-  if (patch_eligible(g, (int)x.element_size())) {
-    auto r = conv_fwd_fused_patch_impl(x, wq, wraw, bias, stride, pad,
-                                       sigma_mode, factor, seed, telem, true);
-    return {r[0], r[1], empty};
+  switch (conv_route(g, (int)x.element_size())) {
+    case ConvRoute::Patch: {
+      auto r = conv_fwd_fused_patch_impl(x, wq, wraw, bias, stride, pad,
+                                         sigma_mode, factor, seed, telem,
+                                         true);
+      return {r[0], r[1], empty};
+    }
+    case ConvRoute::ColSmallK:
+    case ConvRoute::ColGemm:
+      return conv_fwd_fused_col_impl(x, wq, wraw, bias, stride, pad,
+                                     sigma_mode, factor, seed, telem,
+                                     /*want_y=*/true);
+    case ConvRoute::Stream:
+      break;
   }
-  if (g.flat)
-    return conv_fwd_fused_col_impl(x, wq, wraw, bias, stride, pad, sigma_mode,
-                                   factor, seed, telem, /*want_y=*/true);
   auto r = conv_fwd_fused_impl(x, wq, wraw, bias, stride, pad, sigma_mode,
                                factor, seed, telem, /*want_y=*/true);
   return {r[0], r[1], empty};
@@ -2260,17 +2329,37 @@ std::vector<torch::Tensor> sigma_noise_conv(torch::Tensor x, torch::Tensor wraw,
   auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
                      (int)x.size(1), (int)wraw.size(0), (int)wraw.size(2),
                      (int)wraw.size(3), (int)stride, (int)pad);
-  if (patch_eligible(g, (int)x.element_size()))
-    return conv_fwd_fused_patch_impl(x, wraw, wraw, empty_bias, stride, pad,
-                                     sigma_mode, factor, seed, telem, false);
-  if (g.flat) {
-    auto r = conv_fwd_fused_col_impl(x, wraw, wraw, empty_bias, stride, pad,
-                                     sigma_mode, factor, seed, telem,
-                                     /*want_y=*/false);
-    return {r[0], r[1]};
+  switch (conv_route(g, (int)x.element_size())) {
+    case ConvRoute::Patch:
+      return conv_fwd_fused_patch_impl(x, wraw, wraw, empty_bias, stride, pad,
+                                       sigma_mode, factor, seed, telem, false);
+    case ConvRoute::ColSmallK:
+    case ConvRoute::ColGemm: {
+      auto r = conv_fwd_fused_col_impl(x, wraw, wraw, empty_bias, stride, pad,
+                                       sigma_mode, factor, seed, telem,
+                                       /*want_y=*/false);
+      return {r[0], r[1]};
+    }
+    case ConvRoute::Stream:
+      break;
   }
   return conv_fwd_fused_impl(x, wraw, wraw, empty_bias, stride, pad,
                              sigma_mode, factor, seed, telem, /*want_y=*/false);
+}
+
+std::string conv_fused_route(int64_t C, int64_t H, int64_t W, int64_t K,
+                             int64_t R, int64_t S, int64_t stride, int64_t pad,
+                             int64_t elem_size) {
+  // the route does not depend on the batch size
+  auto g = make_geom(1, (int)H, (int)W, (int)C, (int)K, (int)R, (int)S,
+                     (int)stride, (int)pad);
+  switch (conv_route(g, (int)elem_size)) {
+    case ConvRoute::Patch: return "patch";
+    case ConvRoute::ColSmallK: return "col_smallk";
+    case ConvRoute::ColGemm: return "col_gemm";
+    case ConvRoute::Stream: break;
+  }
+  return "stream";
 }
 
 // ===========================================================================
