@@ -158,6 +158,9 @@ std::string conv_fused_route(int64_t C, int64_t H, int64_t W, int64_t K,
                              int64_t R, int64_t S, int64_t stride, int64_t pad,
                              int64_t elem_size);
 std::string linear_fused_route(int64_t Kc, int64_t K, int64_t elem_size);
+std::string conv_patch_tile(int64_t C, int64_t H, int64_t W, int64_t K,
+                            int64_t R, int64_t S, int64_t stride, int64_t pad,
+                            int64_t elem_size, int64_t sigma_mode, bool telem);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fake_quant_fwd", &fake_quant_fwd);
@@ -204,6 +207,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_pool_eligible", &conv_pool_eligible);
   m.def("conv_fused_route", &conv_fused_route);
   m.def("linear_fused_route", &linear_fused_route);
+  m.def("conv_patch_tile", &conv_patch_tile);
   m.def("conv_pool_fwd_fused", &conv_pool_fwd_fused);
   m.def("conv_pool_wgrad", &conv_pool_wgrad);
   m.def("im2col_materialize", &im2col_materialize);

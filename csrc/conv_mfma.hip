@@ -9,7 +9,11 @@
 //
 // Structure (v1, correctness-first; tuned against rocprof after):
 //   * block = 256 threads = 4 waves in a 2x2 wave grid
-//   * tile = 64(M) x 64(N), K-step 32, v_mfma_f32_16x16x32_bf16
+//   * tile = 64(M) x 64(N), K-step 32, v_mfma_f32_16x16x32_bf16; the
+//     image-patch forward also has layer-fitted one-block-per-image tiles
+//     (conv_fwd_patch_tile_kernel, chosen by patch_tile): 4 waves over M x
+//     up to 5 N-fragments for plain convs / stride-1 dgrad with K <= 80,
+//     with filter rows that fall wholly into the zero padding skipped
 //   * K-loop runs over filter taps (r,s) outer, input-channel slices inner,
 //     so NHWC staging loads are channel-contiguous (vectorizable) and there
 //     is no im2col materialization
@@ -25,6 +29,9 @@
 #include <torch/extension.h>
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
+#include <cstdlib>
+#include <cstring>
+#include <string>
 #include "common.h"
 
 namespace {
@@ -2091,6 +2098,232 @@ void conv_fwd_patch_kernel(const T* __restrict__ x, const T* __restrict__ wq,
   }
 }
 
+// --------------------------------------------------------------------------
+// Layer-fitted image-patch tiles: ONE block per image covers every output
+// pixel and every output channel, so the image is staged once and no
+// block runs a mostly-empty N tile (conv2 dgrad, K = 65, spent half its
+// grid on one useful column of 64). The 4 waves are laid out WMS over M
+// by 4/WMS over N; a wave owns the 16-row M-fragments  i*WMS + wave%WMS
+// (i < MF) and the 16-column N-fragments  j*(4/WMS) + wave/WMS  (j < NF),
+// interleaved so that tail and skipped fragments spread over the waves.
+// M-fragments stay 16-aligned from pixel 0 and every output element is
+// still one chain of 16x16x32 MFMAs in (r, ck) order, so outputs and the
+// noise draw are bit-identical to the 64x64 kernel above.
+//
+// Row skip: a (M-fragment, filter row r) pair whose 16 pixels all fall in
+// the vertical zero padding (or past MI) would multiply the zero slot;
+// a per-fragment bit mask over r, built wave-uniformly before the round
+// loop, skips its MFMAs (its prefetched A read is one broadcast read of
+// the zero slot). Mixed fragments keep the per-lane zero-slot path.
+//
+// The weight tile is single-buffered (two barriers per round): a second
+// buffer that saves the trailing barrier was measured and costs the third
+// resident block per CU on conv2 dgrad (56 KB vs 50 KB of LDS), 5.1 vs
+// 3.5 ms at batch 32768.
+// 16-bit dtypes, no telemetry (see patch_tile for the host-side choice).
+// --------------------------------------------------------------------------
+
+// Weight tile of NROWS rows (a multiple of 16, so a slot is live for whole
+// waves: the guard is wave-uniform). The image is row-padded to NROWS.
+template <typename T, int WSLOTS, int NROWS>
+DEV_INLINE void load_wtile_regs(T dst[WSLOTS][8], const T* __restrict__ w,
+                                const ConvGeom g, const PatchGeom p, int wid,
+                                int r, int ck) {
+#pragma unroll
+  for (int i = 0; i < WSLOTS; ++i) {
+    if (wid * WAVE + i * kBlock >= NROWS * 4) continue;
+    int idx = threadIdx.x + i * kBlock;
+    int row = idx >> 2;
+    int seg = idx & 3;
+    *(bf16x8*)dst[i] = *(const bf16x8*)(
+        w + ((int64_t)row * g.R + r) * p.Krs + ck + seg * 8);
+  }
+}
+
+template <typename T, int WSLOTS, int NROWS, bool ABS_TRANSFORM,
+          int SIGMA_MODE>
+DEV_INLINE void store_wtile_regs(char* lds, const T src[WSLOTS][8], int wid) {
+#pragma unroll
+  for (int i = 0; i < WSLOTS; ++i) {
+    if (wid * WAVE + i * kBlock >= NROWS * 4) continue;
+    int idx = threadIdx.x + i * kBlock;
+    int row = idx >> 2;
+    int seg = idx & 3;
+    if (!ABS_TRANSFORM) {
+      *(bf16x8*)(lds + row * Mma<T>::STRIDE + seg * 16) =
+          *(const bf16x8*)src[i];
+      continue;
+    }
+    float vals[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float v = fabsf(to_f32(src[i][j]));
+      if (SIGMA_MODE == 2) v = v * v + v;
+      vals[j] = v;
+    }
+    Mma<T>::store8(lds, row, seg * 8, vals);
+  }
+}
+
+template <typename T, int SIGMA_MODE, bool BIAS, int WMS, int MF, int NF>
+__global__ __launch_bounds__(kBlock)
+void conv_fwd_patch_tile_kernel(const T* __restrict__ x,
+                                const T* __restrict__ wq,
+                                const T* __restrict__ wraw,
+                                const float* __restrict__ bias,
+                                T* __restrict__ out, ConvGeom g, PatchGeom p,
+                                const float* __restrict__ factor_p,
+                                uint64_t seed,
+                                const int64_t* __restrict__ seed_base =
+                                    nullptr) {
+  using Frag = typename Mma<T>::frag;
+  constexpr int WNS = 4 / WMS;
+  constexpr int NROWS = WNS * NF * 16;  // weight rows = N extent of the tile
+  constexpr int WSLOTS = (NROWS * 4 + kBlock - 1) / kBlock;
+  constexpr int EB = 2;
+  constexpr int STR = Mma<T>::STRIDE;
+  constexpr int WBUF = NROWS * STR;  // one weight tile
+  seed = graph_seed(seed_base, seed);
+  const float factor = (SIGMA_MODE > 0) ? factor_p[0] : 0.0f;
+  const int n = blockIdx.y;  // image
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* patch = smem;  // H * Wp * C_pad elements + one zero span
+  const int zero_off = g.H * p.Wp * p.C_pad * EB;
+  char* b_lds = smem + zero_off + 128;  // wq tile
+  char* c_lds = b_lds + WBUF;           // sigma-weight tile
+
+  // wave-uniform wave index: every fragment guard below is a scalar branch
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int wmi = wid % WMS, wni = wid / WMS;
+  const int lane = threadIdx.x & (WAVE - 1);
+
+  const int CHW = (p.Kr + BK - 1) / BK;
+  const int ROUNDS = g.R * CHW;
+  T breg[WSLOTS][8], creg[WSLOTS][8];
+  load_wtile_regs<T, WSLOTS, NROWS>(breg, wq, g, p, wid, 0, 0);
+  if (SIGMA_MODE > 0)
+    load_wtile_regs<T, WSLOTS, NROWS>(creg, wraw, g, p, wid, 0, 0);
+
+  stage_patch(patch, x, g, p, n);
+
+  f32x4 acc[MF][NF] = {};
+  f32x4 sacc[MF][NF] = {};
+
+  // hoisted per-fragment pixel decode (as in the 64x64 kernel) and the
+  // wave-uniform mask of filter rows that reach at least one real input
+  // row from this fragment
+  int a_ohs[MF];    // oh*stride - pad, or INT_MIN/2 when m >= MI
+  int a_base[MF];   // ((ohs*Wp + ow*stride) * C_pad) element offset
+  unsigned live[MF];
+#pragma unroll
+  for (int i = 0; i < MF; ++i) {
+    int m_local = (i * WMS + wmi) * 16 + (lane & 15);
+    if (m_local < p.MI) {
+      int ow = m_local % g.OW;
+      int oh = m_local / g.OW;
+      int ohs = oh * g.stride - g.pad;
+      a_ohs[i] = ohs;
+      a_base[i] = (ohs * p.Wp + ow * g.stride) * p.C_pad;
+    } else {
+      a_ohs[i] = INT_MIN / 2;
+      a_base[i] = 0;
+    }
+    unsigned mask = 0;
+    for (int r = 0; r < g.R; ++r) {  // host guarantees R <= 32
+      int ih = a_ohs[i] + r;
+      if (__ballot(ih >= 0 && ih < g.H) != 0) mask |= 1u << r;
+    }
+    live[i] = __builtin_amdgcn_readfirstlane(mask);
+  }
+  const int rowpitch = p.Wp * p.C_pad;
+
+  // The patch never changes, so the A fragments of round t+1 are read
+  // while round t's MFMAs run and their LDS latency is off the round's
+  // critical path. A fully padded (fragment, r) pair reads the zero slot
+  // (one broadcast address) and its MFMAs are skipped.
+  auto load_a = [&](Frag dst[MF], int r, int ck) {
+#pragma unroll
+    for (int i = 0; i < MF; ++i) {
+      int ih = a_ohs[i] + r;
+      int off = zero_off;
+      if (ih >= 0 && ih < g.H) off = (a_base[i] + r * rowpitch + ck) * EB;
+      dst[i] = Mma<T>::load_span(patch + off, lane);
+    }
+  };
+  Frag afrag[MF], anext[MF] = {};
+  __syncthreads();  // patch staged
+  load_a(afrag, 0, 0);
+
+  int r = 0, ck = 0;
+  for (int t = 0; t < ROUNDS; ++t) {
+    store_wtile_regs<T, WSLOTS, NROWS, false, 0>(b_lds, breg, wid);
+    if (SIGMA_MODE > 0)
+      store_wtile_regs<T, WSLOTS, NROWS, true, SIGMA_MODE>(c_lds, creg, wid);
+    __syncthreads();
+    int rn = r, ckn = ck + BK;
+    if (ckn >= p.Kr) { ckn = 0; ++rn; }
+    Frag bfrag[NF], sfrag[NF];
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      int brow = (j * WNS + wni) * 16 + (lane & 15);
+      bfrag[j] = Mma<T>::load(b_lds, brow, lane);
+      if (SIGMA_MODE > 0) sfrag[j] = Mma<T>::load(c_lds, brow, lane);
+    }
+    // prefetch the next round's weights and A fragments under the MFMAs
+    if (t + 1 < ROUNDS) {
+      load_wtile_regs<T, WSLOTS, NROWS>(breg, wq, g, p, wid, rn, ckn);
+      if (SIGMA_MODE > 0)
+        load_wtile_regs<T, WSLOTS, NROWS>(creg, wraw, g, p, wid, rn, ckn);
+      load_a(anext, rn, ckn);
+    }
+#pragma unroll
+    for (int i = 0; i < MF; ++i) {
+      if (!((live[i] >> r) & 1u)) continue;  // wave-uniform row skip
+#pragma unroll
+      for (int j = 0; j < NF; ++j) {
+        Mma<T>::mma(afrag[i], bfrag[j], acc[i][j]);
+        if (SIGMA_MODE > 0) Mma<T>::mma(afrag[i], sfrag[j], sacc[i][j]);
+      }
+    }
+    __syncthreads();  // all B reads done before the next round's store
+#pragma unroll
+    for (int i = 0; i < MF; ++i) afrag[i] = anext[i];
+    r = rn;
+    ck = ckn;
+  }
+
+  // epilogue: the 64x64 kernel's maths on this wave's fragments
+#pragma unroll
+  for (int i = 0; i < MF; ++i) {
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      int mb_local = (i * WMS + wmi) * 16 + 4 * (lane >> 4);
+      int k = (j * WNS + wni) * 16 + (lane & 15);
+      if (mb_local >= p.MI || k >= g.K) continue;
+      float g4[4];
+      if (SIGMA_MODE > 0)
+        gauss4(seed, (uint64_t)(((int64_t)n * p.MI + mb_local) * g.K + k), g4);
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        int m_local = mb_local + reg;
+        if (m_local < p.MI) {
+          int64_t m = (int64_t)n * p.MI + m_local;
+          float y = acc[i][j][reg];
+          if (BIAS) y += bias[k];
+          float v = y;
+          if (SIGMA_MODE > 0) {
+            float sig = fmaxf(sacc[i][j][reg], 0.0f);
+            float noise = g4[reg] * sqrtf(factor * sig);
+            v = y + noise;
+          }
+          out[m * g.K + k] = from_f32<T>(v);
+        }
+      }
+    }
+  }
+}
+
 inline bool patch_eligible(const ConvGeom& g, int elem_bytes) {
   int c_pad = (g.C + 7) & ~7;
   int wp = g.W + 2 * g.pad;
@@ -2119,6 +2352,50 @@ inline ConvRoute conv_route(const ConvGeom& g, int elem_bytes) {
   return ConvRoute::Stream;
 }
 
+// Block tile of the patch route. The one place the choice is made:
+// conv_fwd_fused_patch_impl launches by it and conv_patch_tile reports it.
+//   Plain  (SIGMA_MODE 0, one accumulator set): K <= 80, MI <= 256 ->
+//          4 waves over M, each up to 4 M-fragments x all <= 5 N-fragments
+//          (conv2 dgrad: 13 x 5, 8.3 -> 3.5 ms at batch 32768)
+//   Noisy  (SIGMA_MODE 1/2, two accumulator sets, no telemetry):
+//          K <= 128, MI <= 112 -> 4 waves over N, each 1 or 2 N-fragments
+//          (the N extent is 4 or 8 fragments, zero weight rows past K)
+//          x all <= 7 M-fragments (conv2 forward: 7 x 8). Bit-identical
+//          but SLOWER than the 64x64 tile on conv2 forward (8.6 vs 6.5 ms),
+//          so it runs only under NOISYNET_PATCH_TILE=all.
+//   Generic: the 64x64 tile -- everything else, and every layer under
+//          NOISYNET_PATCH_TILE=generic. The variable is read per call.
+enum class PatchTile { Generic, Plain, Noisy };
+
+struct PatchTileChoice {
+  PatchTile kind;
+  int mfrag, nfrag;  // 16-row / 16-column fragments the layer needs
+  int nf_wave;       // N-fragments per wave (compile-time in the kernel)
+  int nrows;         // weight rows the tile stages = its N extent
+};
+
+inline PatchTileChoice patch_tile(const ConvGeom& g, int elem_bytes,
+                                  int sigma_mode, bool telem, bool want_y) {
+  PatchTileChoice c{PatchTile::Generic, 0, 0, 0, 0};
+  const char* e = getenv("NOISYNET_PATCH_TILE");
+  if (e && strcmp(e, "generic") == 0) return c;
+  const bool all = e && strcmp(e, "all") == 0;
+  if (elem_bytes != 2 || telem || !want_y || g.R > 32) return c;
+  int mi = g.OH * g.OW;
+  c.mfrag = (mi + 15) / 16;
+  c.nfrag = (g.K + 15) / 16;
+  if (sigma_mode == 0 && g.K <= 80 && mi <= 256) {
+    c.kind = PatchTile::Plain;  // every wave owns all N-fragments
+    c.nf_wave = c.nfrag;
+    c.nrows = c.nfrag * 16;
+  } else if (all && sigma_mode > 0 && g.K <= 128 && mi <= 112) {
+    c.kind = PatchTile::Noisy;  // N-fragments dealt out over the 4 waves
+    c.nf_wave = (c.nfrag + 3) / 4;
+    c.nrows = 4 * c.nf_wave * 16;
+  }
+  return c;
+}
+
 // pad the raw-[K,R,S,C] weight view to [K,R,S*C_pad] (tiny tensors)
 inline torch::Tensor pad_weight_raw(const torch::Tensor& w, int c_pad) {
   auto raw = w.permute({0, 2, 3, 1});  // logical [K,C,R,S] cl -> raw view
@@ -2144,6 +2421,70 @@ inline torch::Tensor pad_weight_full(const torch::Tensor& w, int c_pad,
 
 
 namespace {
+
+// Launch of a layer-fitted tile (16-bit T only; the caller checked
+// tile.kind != Generic).
+template <typename T>
+void launch_patch_tile(const PatchTileChoice& tile, const ConvGeom& g,
+                       const PatchGeom& p, const torch::Tensor& x,
+                       torch::Tensor& out, const torch::Tensor& wq_pad,
+                       const torch::Tensor& wraw_pad,
+                       const torch::Tensor& bias_f, bool has_bias,
+                       const torch::Tensor& factor_f, int64_t seed,
+                       int64_t sigma_mode, int k_pad) {
+  if constexpr (sizeof(T) == 2) {
+    // one block per image; patch + one weight tile per accumulator set
+    size_t tlds = (size_t)g.H * p.Wp * p.C_pad * 2 + 128
+                  + (size_t)(sigma_mode > 0 ? 2 : 1) * k_pad * Mma<T>::STRIDE;
+    auto stream = c10::hip::getCurrentHIPStream();
+    const T* wqp = (const T*)wq_pad.data_ptr();
+    const T* wrp = (sigma_mode > 0) ? (const T*)wraw_pad.data_ptr() : wqp;
+    const float* bp = has_bias ? bias_f.data_ptr<float>() : nullptr;
+    auto launch = [&](auto kfn) {
+      if (tlds > 64 * 1024)
+        hipFuncSetAttribute((const void*)kfn,
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)tlds);
+      hipLaunchKernelGGL(kfn, dim3(1, g.N), dim3(kBlock), tlds, stream,
+                         (const T*)x.data_ptr(), wqp, wrp, bp,
+                         (T*)out.data_ptr(), g, p,
+                         factor_f.data_ptr<float>(), (uint64_t)seed,
+                         g_seed_base);
+    };
+    // <SIGMA_MODE, BIAS, waves over M, M-frags/wave, N-frags/wave>
+    auto plain = [&](auto nf) {
+      constexpr int NFW = decltype(nf)::value;
+      if (has_bias) launch(&conv_fwd_patch_tile_kernel<T, 0, true, 4, 4, NFW>);
+      else launch(&conv_fwd_patch_tile_kernel<T, 0, false, 4, 4, NFW>);
+    };
+    auto noisy = [&](auto sm, auto nf) {
+      constexpr int SM = decltype(sm)::value;
+      constexpr int NFW = decltype(nf)::value;
+      if (has_bias) launch(&conv_fwd_patch_tile_kernel<T, SM, true, 1, 7, NFW>);
+      else launch(&conv_fwd_patch_tile_kernel<T, SM, false, 1, 7, NFW>);
+    };
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    using I3 = std::integral_constant<int, 3>;
+    using I4 = std::integral_constant<int, 4>;
+    using I5 = std::integral_constant<int, 5>;
+    if (tile.kind == PatchTile::Plain) {
+      switch (tile.nf_wave) {
+        case 1: plain(I1{}); break;
+        case 2: plain(I2{}); break;
+        case 3: plain(I3{}); break;
+        case 4: plain(I4{}); break;
+        default: plain(I5{}); break;
+      }
+    } else if (sigma_mode == 1) {
+      if (tile.nf_wave == 1) noisy(I1{}, I1{}); else noisy(I1{}, I2{});
+    } else {
+      if (tile.nf_wave == 1) noisy(I2{}, I1{}); else noisy(I2{}, I2{});
+    }
+  } else {
+    TORCH_CHECK(false, "conv_fwd_patch: layer-fitted tiles are 16-bit only");
+  }
+}
 
 std::vector<torch::Tensor> conv_fwd_fused_patch_impl(
     torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
@@ -2178,7 +2519,11 @@ std::vector<torch::Tensor> conv_fwd_fused_patch_impl(
   auto factor_f = factor.to(torch::kFloat32).reshape({1}).contiguous();
   // fully padded weight image (rows to the k-tile multiple, columns to
   // round32): staging loads become unconditional 16-B vectors
-  int k_pad = (g.K + BN - 1) / BN * BN;
+  const PatchTileChoice tile = patch_tile(g, (int)x.element_size(),
+                                          (int)sigma_mode, telem, want_y);
+  // weight rows follow the N extent of the chosen tile
+  int k_pad = tile.kind == PatchTile::Generic ? (g.K + BN - 1) / BN * BN
+                                              : tile.nrows;
   auto wq_pad = want_y ? pad_weight_full(wq, p.C_pad, k_pad, p.Krs)
                        : torch::Tensor();
   auto wraw_pad = (sigma_mode > 0)
@@ -2188,6 +2533,11 @@ std::vector<torch::Tensor> conv_fwd_fused_patch_impl(
   dim3 grid((g.K + BN - 1) / BN, g.N);
   NN_DISPATCH(x.scalar_type(), "conv_fwd_patch", [&] {
     using T = typename DevT<scalar_t>::type;
+    if (tile.kind != PatchTile::Generic) {
+      launch_patch_tile<T>(tile, g, p, x, out, wq_pad, wraw_pad, bias_f,
+                           has_bias, factor_f, seed, sigma_mode, k_pad);
+      return;
+    }
     lds = (size_t)g.H * p.Wp * p.C_pad * sizeof(T) + 128
           + (size_t)3 * BN * Mma<T>::STRIDE;
     auto stream = c10::hip::getCurrentHIPStream();
@@ -2360,6 +2710,21 @@ std::string conv_fused_route(int64_t C, int64_t H, int64_t W, int64_t K,
     case ConvRoute::Stream: break;
   }
   return "stream";
+}
+
+// Block tile conv_fwd_fused runs this layer with on the patch route:
+// "<M-fragments>x<N-fragments>" for a layer-fitted one-block-per-image
+// tile, "generic" for the 64x64 tile, "none" off the patch route.
+std::string conv_patch_tile(int64_t C, int64_t H, int64_t W, int64_t K,
+                            int64_t R, int64_t S, int64_t stride, int64_t pad,
+                            int64_t elem_size, int64_t sigma_mode,
+                            bool telem) {
+  auto g = make_geom(1, (int)H, (int)W, (int)C, (int)K, (int)R, (int)S,
+                     (int)stride, (int)pad);
+  if (conv_route(g, (int)elem_size) != ConvRoute::Patch) return "none";
+  auto t = patch_tile(g, (int)elem_size, (int)sigma_mode, telem, true);
+  if (t.kind == PatchTile::Generic) return "generic";
+  return std::to_string(t.mfrag) + "x" + std::to_string(t.nfrag);
 }
 
 // ===========================================================================
