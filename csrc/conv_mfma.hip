@@ -3165,3 +3165,499 @@ torch::Tensor conv_wgrad_from_col(torch::Tensor gy, torch::Tensor col,
                 .contiguous(at::MemoryFormat::ChannelsLast);
   return dw;
 }
+
+// ===========================================================================
+// Tiled crossbars: per-block current noise and ADC in one fused MFMA VMM.
+//
+// The contraction (crossbar rows) runs over the flat (r, s, c) filter order,
+// c fastest -- for a linear layer the input index -- and is cut into blocks
+// of xbar_rows rows (a positive multiple of the 32-row k-step; the last block
+// may be short). Per block b and output (m, k):
+//   p_b = sum x * wq                  s_b = max(sum x * f(|w_raw|), 0)
+//   v_b = p_b + eps_b * sqrt(factor * s_b)       eps_b ~ N(0,1) per block
+//   q_b = step * clamp(rint(v_b * inv_step), -Qm, Qm)
+//   out = sum_b q_b + bias            (fp32, b ascending; rounded once)
+// The block epilogue runs in registers on the live 2x2 accumulator fragments
+// every xbar_rows/32 k-steps; no partial sum reaches memory. The Philox
+// counter of a four-row group is (b*M + m)*K + k, so block 0 draws what the
+// unblocked kernels draw and every block has counters of its own.
+// Same 64x64 tile / 4 waves / BK = 32 structure as conv_fwd_kernel.
+// ===========================================================================
+
+namespace {
+
+// The output pixel a thread stages (fixed for the whole contraction) and the
+// (r, s, c) position of the first of its 8 crossbar rows in the current
+// k-step, advanced by 32 rows per step without a division.
+struct XbarRow {
+  bool live;        // pixel inside M
+  int img, ih0, iw0;
+  int r, s, c;
+};
+
+DEV_INLINE void xbar_row_advance(XbarRow& p, const ConvGeom& g, int rows) {
+  p.c += rows;
+  while (p.c >= g.C) {
+    p.c -= g.C;
+    if (++p.s == g.S) {
+      p.s = 0;
+      ++p.r;
+    }
+  }
+}
+
+// One thread's share of a k-step, held in registers between its global loads
+// and its LDS stores so the next step's loads fly under this step's MFMAs:
+// 8 activations, 8 wq and 8 w_raw elements.
+template <typename T>
+struct XbarRegs {
+  alignas(16) T x[8];
+  alignas(16) T q[8];
+  alignas(16) T w[8];
+};
+
+// activations: 8 consecutive crossbar rows from (r, s, c) on of the thread's
+// output pixel. A span inside one filter tap is 16 contiguous bytes for a
+// 16-bit dtype: one load (memcpy form, since for C % 8 != 0 the address is
+// only element-aligned). A span that straddles taps, or runs past the last
+// row (r reaches R), walks element by element; padding positions are zeros.
+template <typename T>
+DEV_INLINE void xbar_load_x(T (&v)[8], const T* __restrict__ x,
+                            const ConvGeom& g, const XbarRow& p) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = from_f32<T>(0.0f);
+  if (!(p.live && p.r < g.R)) return;
+  if (p.c + 8 <= g.C) {
+    int ih = p.ih0 + p.r, iw = p.iw0 + p.s;
+    if (ih >= 0 && ih < g.H && iw >= 0 && iw < g.W) {
+      const T* px = x + (((int64_t)p.img * g.H + ih) * g.W + iw) * g.C + p.c;
+      if (sizeof(T) == 2) {
+        __builtin_memcpy(v, px, 16);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = px[j];
+      }
+    }
+  } else {
+    int r = p.r, s = p.s, c = p.c;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      int ih = p.ih0 + r, iw = p.iw0 + s;
+      if (r < g.R && ih >= 0 && ih < g.H && iw >= 0 && iw < g.W)
+        v[j] = x[(((int64_t)p.img * g.H + ih) * g.W + iw) * g.C + c];
+      if (++c == g.C) {
+        c = 0;
+        if (++s == g.S) {
+          s = 0;
+          ++r;
+        }
+      }
+    }
+  }
+}
+
+// weights from the [K, pitch] row matrices. For 16-bit dtypes the host pads
+// rows with zeros to pitch % 8 == 0, so every 8-span is one aligned 16-byte
+// load or lies wholly past the row.
+template <typename T, int SIGMA_MODE>
+DEV_INLINE void xbar_load_w(T (&q)[8], T (&w)[8], const T* __restrict__ wq,
+                            const T* __restrict__ wraw, int K, int n0, int ck,
+                            int nrows, int pitch) {
+  int k = n0 + (threadIdx.x >> 2);
+  int c0 = ck + (threadIdx.x & 3) * 8;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    q[j] = from_f32<T>(0.0f);
+    w[j] = from_f32<T>(0.0f);
+  }
+  if (k >= K) return;
+  const T* pq = wq + (int64_t)k * pitch + c0;
+  const T* pr = wraw + (int64_t)k * pitch + c0;
+  if (sizeof(T) == 2 && (pitch & 7) == 0) {
+    if (c0 + 8 <= pitch) {
+      *(bf16x8*)q = *(const bf16x8*)pq;
+      if (SIGMA_MODE > 0) *(bf16x8*)w = *(const bf16x8*)pr;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (c0 + j < nrows) {
+        q[j] = pq[j];
+        if (SIGMA_MODE > 0) w[j] = pr[j];
+      }
+    }
+  }
+}
+
+template <typename T>
+DEV_INLINE void xbar_put8(char* lds, int row, int seg, const T (&v)[8]) {
+  if (sizeof(T) == 2) {
+    *(bf16x8*)(lds + row * Mma<T>::STRIDE + seg * 16) = *(const bf16x8*)v;
+  } else {
+    float f[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = to_f32(v[j]);
+    Mma<T>::store8(lds, row, seg * 8, f);
+  }
+}
+
+// registers -> LDS tiles: x and wq as they are, f(|w_raw|) and (telemetry
+// with abs2) |w_raw| derived from the ONE raw-weight load
+template <typename T, int SIGMA_MODE, bool TELEM>
+DEV_INLINE void xbar_store_tiles(char* a_lds, char* b_lds, char* c_lds,
+                                 char* d_lds, const XbarRegs<T>& rg) {
+  int row = threadIdx.x >> 2;
+  int seg = threadIdx.x & 3;
+  xbar_put8<T>(a_lds, row, seg, rg.x);
+  xbar_put8<T>(b_lds, row, seg, rg.q);
+  if (SIGMA_MODE > 0) {
+    float a[8], v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      a[j] = fabsf(to_f32(rg.w[j]));
+      v[j] = (SIGMA_MODE == 2) ? a[j] * a[j] + a[j] : a[j];
+    }
+    Mma<T>::store8(c_lds, row, seg * 8, v);
+    if (TELEM && SIGMA_MODE == 2) Mma<T>::store8(d_lds, row, seg * 8, a);
+  }
+}
+
+// SIGMA_MODE: 0 noise off, 1 abs, 2 abs2     ADC: quantise every block
+// TELEM: telem[5] = sum sigma_abs, sum |sum_b noise_b|, max clean y,
+//        (unused, see sat_count), max |v_b|; sat_count = number of block
+//        partials with |rint(v_b / step)| > Qm (exact, 64-bit)
+template <typename T, int SIGMA_MODE, bool ADC, bool TELEM, bool BIAS>
+__global__ __launch_bounds__(kBlock)
+void xbar_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
+                     const T* __restrict__ wraw,
+                     const float* __restrict__ bias, T* __restrict__ out,
+                     ConvGeom g, int wpitch, int xbar_rows,
+                     const float* __restrict__ factor_p,
+                     const float* __restrict__ adc_p /* step, 1/step */,
+                     float qm, uint64_t seed, float* __restrict__ telem,
+                     unsigned long long* __restrict__ sat_count,
+                     const int64_t* __restrict__ seed_base) {
+  seed = graph_seed(seed_base, seed);
+  const float factor = (SIGMA_MODE > 0) ? factor_p[0] : 0.0f;
+  const float step = ADC ? adc_p[0] : 1.0f;
+  const float inv_step = ADC ? adc_p[1] : 1.0f;
+  int n0 = blockIdx.x * BN;
+  int64_t m0 = (int64_t)blockIdx.y * BM;
+
+  constexpr int STR = Mma<T>::STRIDE;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* a_lds = smem;                          // BM rows (x)
+  char* b_lds = smem + BM * STR;               // BN rows (wq)
+  char* c_lds = smem + (BM + BN) * STR;        // BN rows (f(|w_raw|))
+  char* d_lds = smem + (BM + 2 * BN) * STR;    // BN rows (|w_raw|, telem)
+
+  int wid = threadIdx.x / WAVE;
+  int wm = wid >> 1, wn = wid & 1;
+  int lane = threadIdx.x & (WAVE - 1);
+
+  // the output pixel this thread stages, decomposed once, and where its
+  // first 8-row span starts
+  XbarRow xr;
+  {
+    int64_t sm = m0 + (threadIdx.x >> 2);
+    xr.live = sm < g.M;
+    int oh = 0, ow = 0;
+    xr.img = 0;
+    if (xr.live) {
+      int64_t t = sm;
+      ow = (int)(t % g.OW); t /= g.OW;
+      oh = (int)(t % g.OH); t /= g.OH;
+      xr.img = (int)t;
+    }
+    xr.ih0 = oh * g.stride - g.pad;
+    xr.iw0 = ow * g.stride - g.pad;
+    xr.r = xr.s = xr.c = 0;
+    xbar_row_advance(xr, g, (threadIdx.x & 3) * 8);
+  }
+
+  f32x4 acc[2][2] = {};     // p_b
+  f32x4 sacc[2][2] = {};    // s_b
+  f32x4 tacc[2][2] = {};    // sigma_abs of the block (telemetry, abs2)
+  f32x4 oacc[2][2] = {};    // sum_b q_b
+  f32x4 ycl[2][2] = {};     // sum_b p_b (telemetry)
+  f32x4 ntot[2][2] = {};    // sum_b noise_b (telemetry)
+  float t_sum_sigma = 0.0f, t_sat = 0.0f, t_vmax = 0.0f;
+
+  const int nrows = g.R * g.S * g.C;
+  const int steps_per_block = xbar_rows / BK;
+  int steps_left = steps_per_block;
+  int b = 0;
+  XbarRegs<T> rg;
+  xbar_load_x(rg.x, x, g, xr);
+  xbar_load_w<T, SIGMA_MODE>(rg.q, rg.w, wq, wraw, g.K, n0, 0, nrows, wpitch);
+  for (int ck = 0; ck < nrows; ck += BK) {
+    xbar_store_tiles<T, SIGMA_MODE, TELEM>(a_lds, b_lds, c_lds, d_lds, rg);
+    __syncthreads();
+    if (ck + BK < nrows) {  // next step's loads, in flight under the MFMAs
+      xbar_row_advance(xr, g, BK);
+      xbar_load_x(rg.x, x, g, xr);
+      xbar_load_w<T, SIGMA_MODE>(rg.q, rg.w, wq, wraw, g.K, n0, ck + BK,
+                                 nrows, wpitch);
+    }
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm) {
+      auto a = Mma<T>::load(a_lds, wm * 32 + fm * 16 + (lane & 15), lane);
+#pragma unroll
+      for (int fn = 0; fn < 2; ++fn) {
+        int brow = wn * 32 + fn * 16 + (lane & 15);
+        auto bq = Mma<T>::load(b_lds, brow, lane);
+        Mma<T>::mma(a, bq, acc[fm][fn]);
+        if (SIGMA_MODE > 0) {
+          auto bs = Mma<T>::load(c_lds, brow, lane);
+          Mma<T>::mma(a, bs, sacc[fm][fn]);
+        }
+        if (TELEM && SIGMA_MODE == 2) {
+          auto bt = Mma<T>::load(d_lds, brow, lane);
+          Mma<T>::mma(a, bt, tacc[fm][fn]);
+        }
+      }
+    }
+    __syncthreads();
+
+    if (--steps_left > 0 && ck + BK < nrows) continue;
+    // block boundary (or the end): noise + ADC on the live fragments
+    steps_left = steps_per_block;
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm) {
+#pragma unroll
+      for (int fn = 0; fn < 2; ++fn) {
+        int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
+        int n = n0 + wn * 32 + fn * 16 + (lane & 15);
+        float g4[4];
+        if (SIGMA_MODE > 0)
+          gauss4(seed, (uint64_t)(((int64_t)b * g.M + mb) * g.K + n), g4);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          float p = acc[fm][fn][reg];
+          float v = p;
+          if (SIGMA_MODE > 0) {
+            float sig = fmaxf(sacc[fm][fn][reg], 0.0f);
+            float noise = g4[reg] * sqrtf(factor * sig);
+            v = p + noise;
+            if (TELEM) {
+              ntot[fm][fn][reg] += noise;
+              if (mb + reg < g.M && n < g.K)
+                t_sum_sigma += (SIGMA_MODE == 2) ? tacc[fm][fn][reg]
+                                                 : sacc[fm][fn][reg];
+            }
+          }
+          float q = v;
+          if (ADC) {
+            float t = rintf(v * inv_step);
+            if (TELEM && mb + reg < g.M && n < g.K && fabsf(t) > qm)
+              t_sat += 1.0f;
+            q = step * fminf(fmaxf(t, -qm), qm);
+          }
+          if (TELEM) {
+            ycl[fm][fn][reg] += p;
+            if (mb + reg < g.M && n < g.K) t_vmax = fmaxf(t_vmax, fabsf(v));
+          }
+          oacc[fm][fn][reg] += q;
+        }
+        acc[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        sacc[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        tacc[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      }
+    }
+    ++b;
+  }
+
+  // bias, the one rounding to the dtype, stores
+  float t_sum_noise = 0.0f, t_max_y = -INFINITY;
+#pragma unroll
+  for (int fm = 0; fm < 2; ++fm) {
+#pragma unroll
+    for (int fn = 0; fn < 2; ++fn) {
+      int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
+      int n = n0 + wn * 32 + fn * 16 + (lane & 15);
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        int64_t m = mb + reg;
+        if (m < g.M && n < g.K) {
+          float bv = BIAS ? bias[n] : 0.0f;
+          out[m * g.K + n] = from_f32<T>(oacc[fm][fn][reg] + bv);
+          if (TELEM) {
+            t_sum_noise += fabsf(ntot[fm][fn][reg]);
+            t_max_y = fmaxf(t_max_y, ycl[fm][fn][reg] + bv);
+          }
+        }
+      }
+    }
+  }
+  if (TELEM) {
+    __shared__ float red[4];
+    __shared__ float redm[2][4];
+    float s0 = block_sum(t_sum_sigma, red);
+    __syncthreads();
+    float s1 = block_sum(t_sum_noise, red);
+    __syncthreads();
+    float s3 = block_sum(t_sat, red);  // <= 4096 per epilogue: exact
+    float my = wave_max(t_max_y);
+    float mv = wave_max(t_vmax);
+    if (lane == 0) {
+      redm[0][wid] = my;
+      redm[1][wid] = mv;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      if (SIGMA_MODE > 0) {
+        atomicAdd(&telem[0], s0);
+        atomicAdd(&telem[1], s1);
+      }
+      atomic_max_f32(&telem[2], fmaxf(fmaxf(redm[0][0], redm[0][1]),
+                                      fmaxf(redm[0][2], redm[0][3])));
+      if (ADC) atomicAdd(sat_count, (unsigned long long)(s3 + 0.5f));
+      atomic_max_f32(&telem[4], fmaxf(fmaxf(redm[1][0], redm[1][1]),
+                                      fmaxf(redm[1][2], redm[1][3])));
+    }
+  }
+}
+
+void check_xbar_args(int64_t sigma_mode, int64_t xbar_rows, int64_t adc_bits,
+                     const torch::Tensor& adc, const torch::Tensor& x,
+                     const char* who) {
+  check_sigma_mode(sigma_mode, true, who);
+  TORCH_CHECK(xbar_rows > 0 && xbar_rows % BK == 0, who,
+              ": xbar_rows must be a positive multiple of ", BK, ", got ",
+              xbar_rows);
+  TORCH_CHECK(adc_bits == 0 || (adc_bits >= 2 && adc_bits <= 16), who,
+              ": adc_bits must be 0 or 2..16, got ", adc_bits);
+  TORCH_CHECK(sigma_mode != 0 || adc_bits != 0, who,
+              ": noise (sigma_mode) and ADC (adc_bits) are both off");
+  if (adc_bits > 0)
+    TORCH_CHECK(adc.numel() == 2 && adc.scalar_type() == torch::kFloat32 &&
+                    adc.is_contiguous() && adc.device() == x.device(),
+                who, ": adc must be the fp32 device tensor [step, 1/step]");
+}
+
+// x, wq2, wr2 are raw NHWC / [K, nrows] row-matrix views; out is allocated by
+// the caller with M*K elements in [M, K] raw order
+std::vector<torch::Tensor> xbar_fwd_impl(
+    const torch::Tensor& x, torch::Tensor wq2, torch::Tensor wr2,
+    const torch::Tensor& bias, ConvGeom g, torch::Tensor out,
+    int64_t sigma_mode, const torch::Tensor& factor, int64_t xbar_rows,
+    int64_t adc_bits, const torch::Tensor& adc, int64_t seed, bool telem,
+    const char* who) {
+  check_xbar_args(sigma_mode, xbar_rows, adc_bits, adc, x, who);
+  int nrows = g.R * g.S * g.C;
+  TORCH_CHECK(wq2.dim() == 2 && wq2.size(0) == g.K && wq2.size(1) == nrows &&
+                  wr2.sizes() == wq2.sizes(),
+              who, ": weight shape mismatch");
+  TORCH_CHECK(wq2.scalar_type() == x.scalar_type() &&
+                  wr2.scalar_type() == x.scalar_type(),
+              who, ": x and the weights must share one dtype");
+  int pitch = nrows;
+  if (x.element_size() == 2 && (nrows & 7) != 0) {
+    // zero-pad the (small) weight rows so the kernel's 16-byte row loads
+    // are aligned
+    pitch = (nrows + 7) & ~7;
+    bool same = wr2.is_same(wq2);
+    wq2 = at::constant_pad_nd(wq2, {0, pitch - nrows}, 0);
+    wr2 = same ? wq2 : at::constant_pad_nd(wr2, {0, pitch - nrows}, 0);
+  }
+  wq2 = wq2.contiguous();
+  wr2 = wr2.contiguous();
+  bool has_bias = bias.numel() > 0;
+  if (has_bias) TORCH_CHECK(bias.numel() == g.K, who, ": bias size mismatch");
+  torch::Tensor bias_f;
+  if (has_bias) bias_f = bias.to(torch::kFloat32).contiguous();
+  auto f32 = x.options().dtype(torch::kFloat32);
+  torch::Tensor tele, sat;
+  if (telem) {
+    tele = torch::zeros({5}, f32);
+    tele[2] = -std::numeric_limits<float>::infinity();
+    sat = torch::zeros({1}, x.options().dtype(torch::kLong));
+  } else {
+    tele = torch::empty({0}, f32);
+  }
+  auto factor_f = factor.to(torch::kFloat32).reshape({1}).contiguous();
+  bool adc_on = adc_bits > 0;
+  float qm = adc_on ? (float)((1 << (adc_bits - 1)) - 1) : 0.0f;
+  dim3 grid((g.K + BN - 1) / BN, (int)((g.M + BM - 1) / BM));
+  NN_DISPATCH(x.scalar_type(), "xbar_fwd", [&] {
+    using T = typename DevT<scalar_t>::type;
+    size_t lds = (size_t)(BM + 3 * BN) * Mma<T>::STRIDE;
+    auto stream = c10::hip::getCurrentHIPStream();
+    const T* xp = (const T*)x.data_ptr();
+    const T* wqp = (const T*)wq2.data_ptr();
+    const T* wrp = (const T*)wr2.data_ptr();
+    const float* bp = has_bias ? bias_f.data_ptr<float>() : nullptr;
+    T* op = (T*)out.data_ptr();
+    float* tp = telem ? tele.data_ptr<float>() : nullptr;
+    unsigned long long* sp =
+        telem ? (unsigned long long*)sat.data_ptr<int64_t>() : nullptr;
+    const float* f = factor_f.data_ptr<float>();
+    const float* ap = adc_on ? adc.data_ptr<float>() : nullptr;
+    uint64_t sd = (uint64_t)seed;
+    auto launch = [&](auto sm, auto ad, auto tl, auto bi) {
+      hipLaunchKernelGGL((xbar_fwd_kernel<T, decltype(sm)::value,
+                          decltype(ad)::value, decltype(tl)::value,
+                          decltype(bi)::value>), grid, dim3(kBlock), lds,
+                         stream, xp, wqp, wrp, bp, op, g, pitch,
+                         (int)xbar_rows, f, ap, qm, sd, tp, sp, g_seed_base);
+    };
+    using TT = std::true_type; using FF = std::false_type;
+    auto with_bias = [&](auto sm, auto ad, auto tl) {
+      if (has_bias) launch(sm, ad, tl, TT{}); else launch(sm, ad, tl, FF{});
+    };
+    auto with_telem = [&](auto sm, auto ad) {
+      if (telem) with_bias(sm, ad, TT{}); else with_bias(sm, ad, FF{});
+    };
+    auto with_adc = [&](auto sm) {
+      if (adc_on) with_telem(sm, TT{}); else with_telem(sm, FF{});
+    };
+    // check_xbar_args left exactly these: 0 (ADC on), 1, 2
+    if (sigma_mode == 0) with_telem(std::integral_constant<int, 0>{}, TT{});
+    else if (sigma_mode == 1) with_adc(std::integral_constant<int, 1>{});
+    else with_adc(std::integral_constant<int, 2>{});
+  });
+  HIP_CHECK_LAST();
+  if (telem) tele.narrow(0, 3, 1).copy_(sat);
+  return {out, tele};
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> xbar_fwd_conv(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
+    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
+    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t seed,
+    bool telem) {
+  check_cl(x, "xbar_fwd_conv x");
+  check_cl(wq, "xbar_fwd_conv wq");
+  check_cl(wraw, "xbar_fwd_conv wraw");
+  TORCH_CHECK(wq.size(1) == x.size(1), "xbar_fwd_conv: channel mismatch");
+  auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
+                     (int)x.size(1), (int)wq.size(0), (int)wq.size(2),
+                     (int)wq.size(3), (int)stride, (int)pad);
+  TORCH_CHECK(g.OH > 0 && g.OW > 0, "xbar_fwd_conv: empty output");
+  auto out = torch::empty({g.N, g.K, g.OH, g.OW},
+                          x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  int64_t nrows = (int64_t)g.R * g.S * g.C;
+  // channels_last [K, C, R, S] is the raw [K, (r, s, c)] row matrix
+  auto rows = [&](const torch::Tensor& w) {
+    return w.permute({0, 2, 3, 1}).reshape({(int64_t)g.K, nrows});
+  };
+  auto wq2 = rows(wq);
+  auto wr2 = wraw.is_same(wq) ? wq2 : rows(wraw);
+  return xbar_fwd_impl(x, wq2, wr2, bias, g, out, sigma_mode, factor,
+                       xbar_rows, adc_bits, adc, seed, telem, "xbar_fwd_conv");
+}
+
+std::vector<torch::Tensor> xbar_fwd_linear(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
+    int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
+    int64_t adc_bits, torch::Tensor adc, int64_t seed, bool telem) {
+  TORCH_CHECK(wq.dim() == 2 && wq.size(1) == x.size(1),
+              "xbar_fwd_linear: weight shape mismatch");
+  auto g = linear_geom(x, wq.size(0));
+  auto out = torch::empty({x.size(0), wq.size(0)}, x.options());
+  return xbar_fwd_impl(x, wq, wraw, bias, g, out, sigma_mode, factor,
+                       xbar_rows, adc_bits, adc, seed, telem,
+                       "xbar_fwd_linear");
+}

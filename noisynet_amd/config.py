@@ -101,6 +101,19 @@ def build_noisynet_parser():
                         help='synthetic-data train set size (no npz present)')
     parser.add_argument('--n_test', type=int, default=10000,
                         help='synthetic-data test set size (no npz present)')
+    # tiled crossbars: every layer's contraction is cut into blocks of
+    # xbar_rows rows (the (r,s,c) filter order / the linear input index),
+    # each with its own current noise and ADC
+    parser.add_argument('--xbar_rows', type=int, default=0, metavar='',
+                        help='crossbar tile rows, a multiple of 32 (0 = one '
+                             'unbounded crossbar per layer)')
+    parser.add_argument('--q_adc', type=int, default=0, metavar='',
+                        help='ADC bits per crossbar tile, 2..16 (0 = no ADC)')
+    parser.add_argument('--adc_max', type=float, default=0.0, metavar='',
+                        help='ADC full-scale range of a tile partial sum')
+    for i in (1, 2, 3, 4):
+        parser.add_argument('--adc_max%d' % i, type=float, default=0.0,
+                            metavar='')
     return parser
 
 
@@ -124,6 +137,9 @@ def broadcast_per_layer(args):
         args.act_max1 = args.act_max2 = args.act_max3 = args.act_max
     if args.w_max > 0:
         args.w_max1 = args.w_max2 = args.w_max3 = args.w_max4 = args.w_max
+    if getattr(args, 'adc_max', 0) > 0:
+        args.adc_max1 = args.adc_max2 = args.adc_max3 = args.adc_max4 = \
+            args.adc_max
     if args.n_w > 0:
         args.n_w1 = args.n_w2 = args.n_w3 = args.n_w4 = args.n_w
     if args.LR_1 == 0:

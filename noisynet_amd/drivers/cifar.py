@@ -229,6 +229,8 @@ def train_one(args, model, train_inputs, train_labels, test_inputs, test_labels,
         model.power = [[] for _ in range(args.num_layers)]
         model.nsr = [[] for _ in range(args.num_layers)]
         model.input_sparsity = [[] for _ in range(args.num_layers)]
+        model.adc_clip = [[] for _ in range(args.num_layers)]
+        model.partial_absmax = [[] for _ in range(args.num_layers)]
         model.train()
         tr_accuracies = []
 
@@ -313,6 +315,8 @@ def train_one(args, model, train_inputs, train_labels, test_inputs, test_labels,
 
         print('{}\tEpoch {:>3d}  Train {:.2f}  Test {:.2f}  LR {:.4f}'.format(
             str(datetime.now())[:-7], epoch, tr_acc, te_acc, lr))
+        if getattr(args, 'xbar_rows', 0) > 0:
+            print_xbar_stats(model, args)
 
         if te_acc > best_accuracy:
             if saved:
@@ -339,6 +343,25 @@ def train_one(args, model, train_inputs, train_labels, test_inputs, test_labels,
             prev_best_acc = best_accuracy
 
     return best_accuracy, best_epoch
+
+
+def print_xbar_stats(model, args):
+    """Per-layer tile statistics of the epoch's first 20 batches: power and
+    NSR of the noisy layers, the share of tile partial sums the ADC clipped,
+    and max |tile partial| -- the figure to pick --adc_max from."""
+    def mean(v):
+        return float(np.mean(v)) if len(v) else float('nan')
+
+    for k in range(args.num_layers):
+        if not model.partial_absmax[k]:
+            continue
+        print('\txbar layer {:d} ({:d} rows/tile, {:d}-bit ADC, adc_max {:g}):'
+              '  power {:.3g}  NSR {:.3g}  clipped {:.2%}  max|partial| {:.4g}'
+              .format(k + 1, args.xbar_rows, args.q_adc,
+                      getattr(args, 'adc_max%d' % (k + 1)),
+                      mean(model.power[k]), mean(model.nsr[k]),
+                      mean(model.adc_clip[k]),
+                      max(model.partial_absmax[k])))
 
 
 def restore_model(args, device):

@@ -24,6 +24,15 @@ two-op composition, so the switch at iteration 20 is invisible. On that path
 the un-pooled activation never exists and ``model.conv1_`` is None; only the
 introspective path and the L2_act/L3_act penalties read it, and those never
 take the fused-pool path. NOISYNET_NO_CONV1_POOL=1 selects the composition.
+
+Tiled crossbars (--xbar_rows N > 0): every layer's contraction is cut into
+blocks of N crossbar rows (the (r, s, c) filter order; the input index for a
+linear layer), each with its own current noise (if the layer's current > 0)
+and its own ADC (--q_adc bits over +-adc_max), through ops.xbar_noisy_conv2d /
+xbar_noisy_linear on the hot path. The conv1+pool kernel is bypassed, the
+introspective flags are refused (ValueError), and ``model.adc_clip`` /
+``model.partial_absmax`` collect the first 20 batches' ADC statistics next to
+power / nsr. With --xbar_rows 0 nothing changes.
 """
 
 import torch
@@ -97,15 +106,47 @@ class Net(nn.Module):
         self.power = [[] for _ in range(args.num_layers)]
         self.nsr = [[] for _ in range(args.num_layers)]
         self.input_sparsity = [[] for _ in range(args.num_layers)]
+        # tiled crossbars (--xbar_rows): share of clipped tile partials and
+        # max |tile partial| per layer, first 20 batches like power / nsr
+        self.adc_clip = [[] for _ in range(args.num_layers)]
+        self.partial_absmax = [[] for _ in range(args.num_layers)]
+        self.xbar_rows = getattr(args, 'xbar_rows', 0) or 0
+        if self.xbar_rows > 0:
+            self._check_xbar_args()
 
     # ------------------------------------------------------------------
-    def _introspective(self):
+    _INTROSPECTIVE_BOOLS = ('plot', 'write', 'merge_bn', 'distort_act',
+                            'print_stats', 'train_act_max')
+    _INTROSPECTIVE_FLOATS = ('L2_act1', 'L2_act2', 'L2_act3', 'L2_act4',
+                             'L3_act', 'uniform_ind', 'uniform_dep',
+                             'normal_ind', 'normal_dep')
+
+    def _introspective_flags(self):
         a = self.args
-        return (a.plot or a.write or a.merge_bn or a.distort_act
-                or a.L2_act1 > 0 or a.L2_act2 > 0 or a.L2_act3 > 0
-                or a.L2_act4 > 0 or a.print_stats or a.L3_act > 0
-                or a.train_act_max or a.uniform_ind > 0 or a.uniform_dep > 0
-                or a.normal_ind > 0 or a.normal_dep > 0)
+        return [n for n in self._INTROSPECTIVE_BOOLS if getattr(a, n)] \
+            + [n for n in self._INTROSPECTIVE_FLOATS if getattr(a, n) > 0]
+
+    def _introspective(self):
+        return bool(self._introspective_flags())
+
+    def _check_xbar_args(self):
+        a = self.args
+        q_adc = getattr(a, 'q_adc', 0) or 0
+        adc_max = [getattr(a, 'adc_max%d' % k, 0.0) for k in (1, 2, 3, 4)]
+        if self.xbar_rows % 32:
+            raise ValueError('--xbar_rows must be a positive multiple of 32, '
+                             'got %d' % self.xbar_rows)
+        if not (q_adc == 0 or 2 <= q_adc <= 16):
+            raise ValueError('--q_adc must be 0 or 2..16, got %d' % q_adc)
+        if q_adc > 0 and not all(m > 0 for m in adc_max):
+            raise ValueError('--q_adc > 0 needs --adc_max (or every '
+                             '--adc_max1..4) > 0, got %s' % adc_max)
+        flags = self._introspective_flags()
+        if flags:
+            raise ValueError(
+                '--xbar_rows %d cannot be combined with --%s: that flag runs '
+                'the introspective forward, which models one unbounded '
+                'crossbar per layer' % (self.xbar_rows, flags[0]))
 
     def _conv1_pool_fused(self, x, i):
         """conv1 and its max-pool run as one kernel (see module docstring)."""
@@ -157,6 +198,56 @@ class Net(nn.Module):
             self.input_sparsity[layer_num].append(float(telem.input_sparsity))
         return out
 
+    def _xbar_layer(self, x, layer, current, merged_dac, i, layer_num,
+                    is_conv):
+        """The layer on tiled crossbars: per-tile noise when its current is
+        > 0 and per-tile ADC when --q_adc > 0 (ops.xbar_noisy_*). A layer with
+        neither is the plain layer, which tiling does not change."""
+        a = self.args
+        q_adc = getattr(a, 'q_adc', 0) or 0
+        if current <= 0 and q_adc == 0:
+            return layer(x)
+        adc_max = getattr(a, 'adc_max%d' % (layer_num + 1), 0.0)
+        w_raw = layer.weight
+        wq, bias = layer.effective_weight()
+        want_telemetry = i < 20
+        sigma_mode, factor, power_denom = None, 0.0, 1.0
+        if current > 0:
+            with torch.no_grad():
+                if merged_dac:
+                    w_max = w_raw.detach().abs().max()
+                    factor = 0.1 * w_max / current
+                    sigma_mode = 'abs'
+                    power_denom = (x.detach().max() * w_max if want_telemetry
+                                   else w_max)
+                else:
+                    input_max = x.detach().max()
+                    factor = 0.1 * input_max / current
+                    sigma_mode = 'abs2'
+                    power_denom = input_max
+        telem = ops.XbarTelemetry() if want_telemetry else None
+        if is_conv:
+            out = ops.xbar_noisy_conv2d(
+                x, wq, w_raw.detach(), bias, 1, 0, sigma_mode, factor,
+                self.xbar_rows, q_adc, adc_max, current=current,
+                power_denom=power_denom, want_telemetry=want_telemetry,
+                telemetry_out=telem)
+        else:
+            out = ops.xbar_noisy_linear(
+                x, wq, w_raw.detach(), bias, sigma_mode, factor,
+                self.xbar_rows, q_adc, adc_max, current=current,
+                power_denom=power_denom, want_telemetry=want_telemetry,
+                telemetry_out=telem)
+        if want_telemetry:
+            if telem.power is not None:
+                self.power[layer_num].append(float(telem.power))
+                self.nsr[layer_num].append(float(telem.nsr))
+                self.input_sparsity[layer_num].append(
+                    float(telem.input_sparsity))
+            self.adc_clip[layer_num].append(float(telem.adc_clip_share))
+            self.partial_absmax[layer_num].append(float(telem.partial_absmax))
+        return out
+
     def _bn_act(self, x, bn, act_max):
         """Fused BN + ReLU + clip."""
         return ops.bn_act(x, bn.weight, bn.bias, bn.running_mean,
@@ -168,6 +259,9 @@ class Net(nn.Module):
     # ------------------------------------------------------------------
     def forward(self, input, epoch=0, i=0, s=0, acc=0.0):
         args = self.args
+        if self.xbar_rows > 0:
+            self._check_xbar_args()   # args may have changed since __init__
+            return self._forward_fused(input, i)
         if not self._introspective():
             return self._forward_fused(input, i)
         return self._forward_reference(input, epoch, i, s, acc)
@@ -179,7 +273,14 @@ class Net(nn.Module):
         x = self.quantize1(input) if args.q_a1 > 0 else input
         self.input = x
 
-        if self._conv1_pool_fused(x, i):
+        xbar = self.xbar_rows > 0
+        if xbar:
+            # tiled crossbars bypass the conv1+pool single-kernel route
+            x = self._xbar_layer(x, self.conv1, args.current1,
+                                 args.merged_dac, i, 0, True)
+            self.conv1_ = x
+            x = ops.maxpool2x2(x)
+        elif self._conv1_pool_fused(x, i):
             x = self._noisy_layer_fused(x, self.conv1, args.current1,
                                         args.merged_dac, i, 0, True, pool=True)
             self.conv1_ = None
@@ -200,7 +301,10 @@ class Net(nn.Module):
         if args.q_a2 > 0:
             x = self.quantize2(x)
 
-        if args.current2 > 0:
+        if xbar:
+            x = self._xbar_layer(x, self.conv2, args.current2, False, i, 1,
+                                 True)
+        elif args.current2 > 0:
             x = self._noisy_layer_fused(x, self.conv2, args.current2,
                                         False, i, 1, True)
         else:
@@ -218,7 +322,10 @@ class Net(nn.Module):
         if args.q_a3 > 0:
             x = self.quantize3(x)
 
-        if args.current3 > 0:
+        if xbar:
+            x = self._xbar_layer(x, self.linear1, args.current3,
+                                 args.merged_dac, i, 2, False)
+        elif args.current3 > 0:
             x = self._noisy_layer_fused(x, self.linear1, args.current3,
                                         args.merged_dac, i, 2, False)
         else:
@@ -233,7 +340,10 @@ class Net(nn.Module):
         if args.q_a4 > 0:
             x = self.quantize4(x)
 
-        if args.current4 > 0:
+        if xbar:
+            x = self._xbar_layer(x, self.linear2, args.current4, False, i, 3,
+                                 False)
+        elif args.current4 > 0:
             x = self._noisy_layer_fused(x, self.linear2, args.current4,
                                         False, i, 3, False)
         else:

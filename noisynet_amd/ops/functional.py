@@ -599,6 +599,217 @@ def fused_noisy_linear(x, wq, w_raw, bias, sigma_mode, factor, current=0.0,
 
 
 # ---------------------------------------------------------------------------
+# Tiled crossbars: the contraction is cut into blocks of xbar_rows rows, each
+# with its own current noise and its own ADC; the digital side adds the blocks
+# ---------------------------------------------------------------------------
+
+
+class XbarTelemetry(NoiseTelemetry):
+    """NoiseTelemetry of a tiled-crossbar call plus the ADC statistics:
+    ``adc_clip_share`` (share of block partials beyond the ADC range) and
+    ``partial_absmax`` (max |v_b| over every block partial -- the value to
+    pick ``adc_max`` from). power / nsr stay None when the noise is off."""
+
+    __slots__ = ("adc_clip_share", "partial_absmax")
+
+    def __init__(self, power=None, nsr=None, input_sparsity=None,
+                 adc_clip_share=None, partial_absmax=None):
+        super().__init__(power, nsr, input_sparsity)
+        self.adc_clip_share = adc_clip_share
+        self.partial_absmax = partial_absmax
+
+
+_XBAR_MODE = {None: 0, "abs": 1, "abs2": 2}
+
+
+def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
+                  sigma_mode, factor, xbar_rows, adc_bits, adc_max,
+                  want_telemetry):
+    """Shared forward of the two xbar Functions. Returns (y, tele) with tele a
+    dict of 0-dim tensors (or None): sigma_abs, abs_noise, max_y, clipped,
+    n_partials, partial_absmax -- sums over the whole call."""
+    x = x2_or_x
+    adc = ref.xbar_adc_params(adc_bits, adc_max, x.device)
+    n_rows = wq[0].numel()
+    nblocks = -(-n_rows // int(xbar_rows))
+    if use_native(x, wq):
+        empty = torch.empty(0, device=x.device, dtype=x.dtype)
+        empty_f = torch.empty(0, device=x.device, dtype=torch.float32)
+        common = (_XBAR_MODE[sigma_mode],
+                  _factor_tensor(factor, x.device) if sigma_mode is not None
+                  else torch.zeros(1, device=x.device, dtype=torch.float32),
+                  int(xbar_rows), int(adc_bits),
+                  adc if adc is not None else empty_f,
+                  _next_seed(x.device), bool(want_telemetry))
+        wr = w_raw if sigma_mode is not None else wq
+        if is_conv:
+            y, t = ext().xbar_fwd_conv(
+                _nhwc(x), _nhwc(wq), _nhwc(wr),
+                bias if bias is not None else empty, stride, padding, *common)
+        else:
+            y, t = ext().xbar_fwd_linear(
+                x.contiguous(), wq.contiguous(), wr.contiguous(),
+                bias if bias is not None else empty, *common)
+        tele = None
+        if want_telemetry:
+            tele = dict(sigma_abs=t[0], abs_noise=t[1], max_y=t[2],
+                        clipped=t[3], n_partials=nblocks * y.numel(),
+                        partial_absmax=t[4])
+        return y, tele
+    tele = {} if want_telemetry else None
+    with torch.no_grad():
+        xd = x.detach()
+        if is_conv:
+            R, S = wq.shape[2], wq.shape[3]
+            xm = ref.xbar_conv_rows(xd.float(), R, S, stride, padding)
+        else:
+            xm = xd
+        ym = ref.xbar_vmm(
+            xm, ref.xbar_weight_rows(wq.detach()),
+            ref.xbar_weight_rows(w_raw.detach()) if sigma_mode is not None
+            else None,
+            bias.detach() if bias is not None else None, sigma_mode, factor,
+            int(xbar_rows), adc_bits, adc, stats=tele)
+        if is_conv:
+            N, K = x.shape[0], wq.shape[0]
+            oh = (x.shape[2] + 2 * padding - R) // stride + 1
+            ow = (x.shape[3] + 2 * padding - S) // stride + 1
+            ym = ym.view(N, oh, ow, K).permute(0, 3, 1, 2)
+        y = ym.to(x.dtype)
+        if is_conv:
+            y = y.contiguous(memory_format=torch.channels_last) if x.is_cuda \
+                else y.contiguous()
+    return y, tele
+
+
+def _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
+                  power_denom):
+    with torch.no_grad():
+        if sigma_mode is not None:
+            telemetry_out.power = 1.2e-6 * current \
+                * (tele["sigma_abs"] / x.shape[0]) / power_denom
+            telemetry_out.nsr = (tele["abs_noise"] / y.numel()) / tele["max_y"]
+        telemetry_out.input_sparsity = (x.detach() > 0).sum() / x.numel()
+        telemetry_out.adc_clip_share = tele["clipped"] / tele["n_partials"]
+        telemetry_out.partial_absmax = tele["partial_absmax"]
+
+
+class _XbarNoisyConv(torch.autograd.Function):
+    """Tiled-crossbar conv: per-block noise + ADC fused into one MFMA pass
+    (xbar_fwd_kernel, csrc/conv_mfma.hip). Backward is the identity straight-through over the
+    noise and the ADC: exactly the gradients of the unblocked conv with wq.
+    A clipped STE would need per-block saturation masks and is not built."""
+
+    @staticmethod
+    def forward(ctx, x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
+                xbar_rows, adc_bits, adc_max, want_telemetry, telemetry_out,
+                current, power_denom):
+        ctx.stride, ctx.padding = stride, padding
+        ctx.has_bias = bias is not None
+        y, tele = _xbar_forward(x, True, wq, w_raw, bias, stride, padding,
+                                sigma_mode, factor, xbar_rows, adc_bits,
+                                adc_max, want_telemetry)
+        if want_telemetry and telemetry_out is not None:
+            _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
+                          power_denom)
+        ctx.save_for_backward(x, wq)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, wq = ctx.saved_tensors
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = ConvDgrad.apply(g, wq, ctx.stride, ctx.padding, x.shape)
+        if ctx.needs_input_grad[1]:
+            gw = ConvWgrad.apply(g, x, ctx.stride, ctx.padding, wq.shape, None)
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            gb = g.sum(dim=(0, 2, 3))
+        return (gx, gw, None, gb) + (None,) * 11
+
+
+class _XbarNoisyLinear(torch.autograd.Function):
+    """Linear twin of _XbarNoisyConv (same kernel, R = S = 1)."""
+
+    @staticmethod
+    def forward(ctx, x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
+                adc_bits, adc_max, want_telemetry, telemetry_out, current,
+                power_denom):
+        ctx.has_bias = bias is not None
+        y, tele = _xbar_forward(x, False, wq, w_raw, bias, 1, 0, sigma_mode,
+                                factor, xbar_rows, adc_bits, adc_max,
+                                want_telemetry)
+        if want_telemetry and telemetry_out is not None:
+            _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
+                          power_denom)
+        ctx.save_for_backward(x, wq)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, wq = ctx.saved_tensors
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = LinearDgrad.apply(g, wq)
+        if ctx.needs_input_grad[1]:
+            gw = LinearWgrad.apply(g, x)
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            gb = g.sum(dim=0)
+        return (gx, gw, None, gb) + (None,) * 9
+
+
+def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
+                      xbar_rows, adc_bits, adc_max, current=0.0,
+                      power_denom=1.0, want_telemetry=False,
+                      telemetry_out=None):
+    """Noisy conv on tiled crossbars.
+
+    The contraction index is the filter's memory order (r, s, c), c fastest;
+    padding positions contribute zero. Block b is rows [b*xbar_rows,
+    min((b+1)*xbar_rows, R*S*C)); ``xbar_rows`` is a positive multiple of 32
+    and the last block may be short. Per block, in fp32,
+        p_b = sum x*wq          s_b = max(sum x*f(|w_raw|), 0)
+        v_b = p_b + eps_b * sqrt(factor * s_b)       eps_b ~ N(0,1) per block
+        q_b = step * clamp(rint(v_b * (1/step)), -Qm, Qm)
+    with Qm = 2^(adc_bits-1) - 1, step = adc_max / Qm, and
+    out = sum_b q_b + bias, rounded once to the dtype. ``sigma_mode`` None
+    switches the noise off (v_b = p_b), ``adc_bits`` 0 the ADC (q_b = v_b);
+    one of the two must be on. ``adc_max`` is a number or a tensor (then it
+    must be positive; it is not read back to check).
+
+    Backward is the identity straight-through over noise and ADC: the
+    gradients are exactly those of conv2d(x, wq, bias). A clipped STE (zero
+    gradient through saturated blocks) would need per-block saturation masks
+    and is out of scope.
+
+    ``telemetry_out`` (an XbarTelemetry) receives power / nsr / sparsity as
+    fused_noisy_conv2d does, plus adc_clip_share and partial_absmax.
+    """
+    if isinstance(stride, (tuple, list)):
+        stride = stride[0]
+    if isinstance(padding, (tuple, list)):
+        padding = padding[0]
+    ref.xbar_check_args(sigma_mode, xbar_rows, adc_bits, adc_max)
+    return _XbarNoisyConv.apply(x, wq, w_raw, bias, stride, padding,
+                                sigma_mode, factor, xbar_rows, adc_bits,
+                                adc_max, want_telemetry, telemetry_out,
+                                current, power_denom)
+
+
+def xbar_noisy_linear(x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
+                      adc_bits, adc_max, current=0.0, power_denom=1.0,
+                      want_telemetry=False, telemetry_out=None):
+    """Noisy linear layer on tiled crossbars: xbar_noisy_conv2d with the input
+    index as the crossbar row. Same straight-through backward (the gradients
+    of F.linear(x, wq, bias)); a clipped STE is out of scope."""
+    ref.xbar_check_args(sigma_mode, xbar_rows, adc_bits, adc_max)
+    return _XbarNoisyLinear.apply(x, wq, w_raw, bias, sigma_mode, factor,
+                                  xbar_rows, adc_bits, adc_max,
+                                  want_telemetry, telemetry_out, current,
+                                  power_denom)
+
+
+# ---------------------------------------------------------------------------
 # Simplified noise modes (uniform_ind / uniform_dep / normal_ind / normal_dep)
 # hardware_model.py:24-41 -- train-time or --noise_test perturbations.
 # ---------------------------------------------------------------------------

@@ -86,6 +86,134 @@ def vmm_noise(sigmas, factor, gen=None):
 
 
 # ---------------------------------------------------------------------------
+# Tiled crossbars: per-block noise and ADC (ops.xbar_noisy_conv2d / _linear)
+# ---------------------------------------------------------------------------
+
+
+def xbar_check_args(sigma_mode, xbar_rows, adc_bits, adc_max):
+    """Argument rules shared by the Python wrappers of the tiled-crossbar op."""
+    if sigma_mode not in (None, "abs", "abs2"):
+        raise ValueError("sigma_mode must be None, 'abs' or 'abs2', got %r"
+                         % (sigma_mode,))
+    if int(xbar_rows) != xbar_rows or xbar_rows <= 0 or xbar_rows % 32:
+        raise ValueError("xbar_rows must be a positive multiple of 32, got %r"
+                         % (xbar_rows,))
+    if int(adc_bits) != adc_bits or not (adc_bits == 0 or 2 <= adc_bits <= 16):
+        raise ValueError("adc_bits must be 0 (ADC off) or 2..16, got %r"
+                         % (adc_bits,))
+    if adc_bits == 0 and sigma_mode is None:
+        raise ValueError("xbar op with neither noise (sigma_mode) nor an ADC "
+                         "(adc_bits) is the plain conv/linear")
+    if adc_bits > 0 and not isinstance(adc_max, torch.Tensor) \
+            and not float(adc_max) > 0:
+        raise ValueError("adc_max must be > 0 when adc_bits > 0, got %r"
+                         % (adc_max,))
+
+
+def xbar_adc_params(adc_bits, adc_max, device):
+    """fp32 tensor [step, 1/step] with step = adc_max / Qm, both rounded once
+    to fp32 (the values the kernel multiplies with); None with the ADC off."""
+    if adc_bits == 0:
+        return None
+    qm = float(2 ** (int(adc_bits) - 1) - 1)
+    if isinstance(adc_max, torch.Tensor):
+        amax = adc_max.detach().to(device=device, dtype=torch.float32).reshape(1)
+    else:
+        # a fill, not a host-to-device copy: legal under graph capture
+        amax = torch.full((1,), float(adc_max), dtype=torch.float32,
+                          device=device)
+    step = amax / qm
+    return torch.cat([step, 1.0 / step])
+
+
+def xbar_conv_rows(x, R, S, stride, padding):
+    """im2col matrix [N*OH*OW, R*S*C] of an NCHW input with the contraction
+    index in the filter's memory order (r, s, c), c fastest -- the crossbar
+    row order. Padding positions are zeros."""
+    N, C = x.shape[0], x.shape[1]
+    cols = F.unfold(x, (R, S), padding=padding, stride=stride)  # (c, r, s)
+    L = cols.shape[-1]
+    cols = cols.view(N, C, R * S, L).permute(0, 3, 2, 1)        # n, l, rs, c
+    return cols.reshape(N * L, R * S * C)
+
+
+def xbar_weight_rows(w):
+    """[K, C, R, S] filter -> [K, R*S*C] in the (r, s, c) row order."""
+    if w.dim() == 2:
+        return w
+    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+
+
+def xbar_vmm(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows, adc_bits,
+             adc, gen=None, stats=None):
+    """Blocked analog VMM on row matrices: xm [M, n], wqm / wrm [K, n].
+
+    Block b covers rows [b*xbar_rows, min((b+1)*xbar_rows, n)). Per block
+        p_b = x_b @ wq_b^T                       s_b = max(x_b @ f(|w_raw,b|)^T, 0)
+        v_b = p_b + eps_b * sqrt(factor * s_b)   (eps_b iid N(0,1) per block)
+        q_b = step * clamp(rint(v_b * (1/step)), -Qm, Qm)
+    and out = sum_b q_b + bias, all in fp32 (b ascending). ``adc`` is the
+    [step, 1/step] tensor of xbar_adc_params (None = ADC off, q_b = v_b);
+    sigma_mode None = noise off. ``stats`` (a dict) receives the telemetry
+    sums: sigma_abs, abs_noise (of the summed block noises), max_y (clean,
+    with bias), clipped (count of |rint(v_b/step)| > Qm), n_partials and
+    partial_absmax (max |v_b|). Returns fp32 [M, K]."""
+    xm, wqm = xm.float(), wqm.float()
+    n = xm.shape[1]
+    M, K = xm.shape[0], wqm.shape[0]
+    out = torch.zeros(M, K, dtype=torch.float32, device=xm.device)
+    if sigma_mode is not None:
+        aw = wrm.float().abs()
+        fw = aw * aw + aw if sigma_mode == "abs2" else aw
+        factor = torch.as_tensor(factor, dtype=torch.float32, device=xm.device)
+    if adc is not None:
+        step, inv_step = adc[0], adc[1]
+        qm = float(2 ** (int(adc_bits) - 1) - 1)
+    if stats is not None:
+        clean = torch.zeros_like(out)
+        noise_tot = torch.zeros_like(out)
+        sig_abs = out.new_zeros(())
+        clipped = 0
+        absmax = out.new_zeros(())
+        nblk = 0
+    for k0 in range(0, n, xbar_rows):
+        k1 = min(k0 + xbar_rows, n)
+        xb = xm[:, k0:k1]
+        p = xb @ wqm[:, k0:k1].t()
+        v = p
+        if sigma_mode is not None:
+            s = (xb @ fw[:, k0:k1].t()).clamp_min(0)
+            eps = torch.randn(p.shape, dtype=torch.float32, device=p.device,
+                              generator=gen)
+            nb = eps * (factor * s).sqrt()
+            v = p + nb
+        if adc is not None:
+            t = torch.round(v * inv_step)
+            q = step * t.clamp(-qm, qm)
+        else:
+            q = v
+        out = out + q
+        if stats is not None:
+            nblk += 1
+            clean = clean + p
+            absmax = torch.maximum(absmax, v.abs().max())
+            if sigma_mode is not None:
+                noise_tot = noise_tot + nb
+                sig_abs = sig_abs + (xb @ aw[:, k0:k1].t()).sum()
+            if adc is not None:
+                clipped = clipped + (t.abs() > qm).sum()
+    if bias is not None:
+        out = out + bias.float()
+    if stats is not None:
+        if bias is not None:
+            clean = clean + bias.float()
+        stats.update(sigma_abs=sig_abs, abs_noise=noise_tot.abs().sum(),
+                     max_y=clean.max(), clipped=clipped,
+                     n_partials=nblk * M * K, partial_absmax=absmax)
+    return out
+
+
+# ---------------------------------------------------------------------------
 # Fused BN + activation (reference composition)
 # ---------------------------------------------------------------------------
 

@@ -1,0 +1,266 @@
+#!/usr/bin/env python3
+"""Time the fused tiled-crossbar op against its two neighbours on the GPU.
+
+At the flagship's own shapes at batch 2048, bf16, noise 'abs2' + 6-bit ADC:
+
+  conv2    x [2048, 65, 14, 14], w [120, 65, 5, 5]   (n = 1625 crossbar rows)
+  linear1  [2048, 3000] x [390, 3000]
+
+and for xbar_rows in {64, 128, 256}:
+
+  (a) xbar      ops.xbar_noisy_conv2d / xbar_noisy_linear: one kernel, every
+                block's noise and ADC in registers
+  (b) unblocked ops.fused_noisy_conv2d / fused_noisy_linear: today's one
+                unbounded crossbar (no ADC; recorded, not a gate)
+  (c) eager     what a user would write without (a): im2col once, then per
+                block slice -> two bf16 matmuls -> randn noise -> round /
+                clamp -> add, every partial through memory
+
+Device events around windows of at least --window seconds after a warm-up,
+the variants alternating over --rounds rounds in one process; the median
+round is reported. Prints one JSON line per (layer, xbar_rows). There is no
+CPU fallback: a time is a GPU time or it is not reported.
+
+--resource-usage needs no GPU: it compiles csrc/conv_mfma.hip for gfx950 with
+-Rpass-analysis=kernel-resource-usage and prints VGPRs, LDS and scratch of
+every xbar_fwd_kernel instantiation.
+"""
+
+import argparse
+import json
+import os
+import re
+import statistics
+import subprocess
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+from noisynet_amd import ops  # noqa: E402
+from noisynet_amd.ops import reference as ref  # noqa: E402
+
+LAYERS = {
+    'conv2': dict(kind='conv', x=(2048, 65, 14, 14), w=(120, 65, 5, 5)),
+    'linear1': dict(kind='linear', x=(2048, 3000), w=(390, 3000)),
+}
+MODE, FACTOR, ADC_BITS, ADC_MAX = 'abs2', 0.05, 6, 3.0
+
+
+def eager_blocked(xm, wq, fw, factor, xbar_rows, step, inv_step, qm,
+                  fp32_matmul=False):
+    """Per-block composition of stock torch ops on row matrices (bf16
+    matmuls, fp32 epilogue; fp32 matmuls for the agreement check, where a
+    partial rounded to bf16 would land on another ADC level)."""
+    if fp32_matmul:
+        xm, wq, fw = xm.float(), wq.float(), fw.float()
+    n = xm.shape[1]
+    out = None
+    for k0 in range(0, n, xbar_rows):
+        k1 = min(k0 + xbar_rows, n)
+        xb = xm[:, k0:k1]
+        p = (xb @ wq[:, k0:k1].t()).float()
+        s = (xb @ fw[:, k0:k1].t()).float().clamp_min(0)
+        v = p + torch.randn_like(p) * (factor * s).sqrt()
+        q = step * torch.round(v * inv_step).clamp(-qm, qm)
+        out = q if out is None else out + q
+    return out
+
+
+def timed(fn, window, min_calls=3):
+    """seconds per call over a window >= ``window``."""
+    calls, total = 0, 0.0
+    while total < window or calls < min_calls:
+        start = torch.cuda.Event(enable_timing=True)
+        stop = torch.cuda.Event(enable_timing=True)
+        start.record()
+        n = fn()
+        stop.record()
+        stop.synchronize()
+        total += start.elapsed_time(stop) / 1e3
+        calls += n
+    return total / calls
+
+
+def bench_layer(name, spec, rows_list, window, rounds, reps):
+    dev, dtype = torch.device('cuda'), torch.bfloat16
+    gen = torch.Generator().manual_seed(0)
+    x = (torch.randint(0, 16, spec['x'], generator=gen).float() / 15).to(dtype)
+    wq = (torch.randn(spec['w'], generator=gen) * 0.1).to(dtype)
+    wr = (torch.randn(spec['w'], generator=gen) * 0.1).to(dtype)
+    x, wq, wr = x.to(dev), wq.to(dev), wr.to(dev)
+    conv = spec['kind'] == 'conv'
+    if conv:
+        x = x.contiguous(memory_format=torch.channels_last)
+        wq = wq.contiguous(memory_format=torch.channels_last)
+        wr = wr.contiguous(memory_format=torch.channels_last)
+    factor = torch.tensor([FACTOR], device=dev)
+    adc = ref.xbar_adc_params(ADC_BITS, ADC_MAX, dev)
+    step, inv_step = adc[0], adc[1]
+    qm = float(2 ** (ADC_BITS - 1) - 1)
+    wq_rows = ref.xbar_weight_rows(wq).contiguous()
+    aw = ref.xbar_weight_rows(wr).abs()
+    fw_rows = (aw * aw + aw).contiguous()
+    n = wq_rows.shape[1]
+
+    def run_unblocked():
+        for _ in range(reps):
+            if conv:
+                ops.fused_noisy_conv2d(x, wq, wr, None, 1, 0, MODE, factor)
+            else:
+                ops.fused_noisy_linear(x, wq, wr, None, MODE, factor)
+        return reps
+
+    results = []
+    for rows in rows_list:
+        def run_xbar():
+            for _ in range(reps):
+                if conv:
+                    ops.xbar_noisy_conv2d(x, wq, wr, None, 1, 0, MODE, factor,
+                                          rows, ADC_BITS, ADC_MAX)
+                else:
+                    ops.xbar_noisy_linear(x, wq, wr, None, MODE, factor, rows,
+                                          ADC_BITS, ADC_MAX)
+            return reps
+
+        def run_eager():
+            xm = ref.xbar_conv_rows(x, spec['w'][2], spec['w'][3], 1, 0) \
+                if conv else x
+            eager_blocked(xm, wq_rows, fw_rows, factor, rows, step, inv_step,
+                          qm)
+            return 1
+
+        variants = {'xbar': run_xbar, 'unblocked': run_unblocked,
+                    'eager': run_eager}
+        with torch.no_grad():
+            # results must agree before speeds are compared: noise off, the
+            # fused op against the eager composition on the same blocks
+            if conv:
+                a = ops.xbar_noisy_conv2d(x, wq, wr, None, 1, 0, None, 0.0,
+                                          rows, ADC_BITS, ADC_MAX)
+                a = a.permute(0, 2, 3, 1).reshape(-1, a.shape[1])
+                xm = ref.xbar_conv_rows(x, spec['w'][2], spec['w'][3], 1, 0)
+            else:
+                a = ops.xbar_noisy_linear(x, wq, wr, None, None, 0.0, rows,
+                                          ADC_BITS, ADC_MAX)
+                xm = x
+            e = eager_blocked(xm, wq_rows, fw_rows,
+                              torch.zeros(1, device=dev), rows, step,
+                              inv_step, qm, fp32_matmul=True)
+            del xm
+            diff = (a.float() - e.float()).abs()
+            moved = float((diff > 0.5 * float(step)).float().mean())
+            for fn in variants.values():    # warm-up: code objects, allocator
+                fn()
+            torch.cuda.synchronize()
+            rr = {k: [] for k in variants}
+            for _ in range(rounds):         # alternate the variants
+                for k, fn in variants.items():
+                    rr[k].append(timed(fn, window))
+        sec = {k: statistics.median(v) for k, v in rr.items()}
+        res = {
+            'bench': 'xbar_adc', 'device': torch.cuda.get_device_name(0),
+            'layer': name, 'x': list(spec['x']), 'w': list(spec['w']),
+            'crossbar_rows_total': n, 'xbar_rows': rows,
+            'blocks': -(-n // rows), 'dtype': 'bf16', 'sigma_mode': MODE,
+            'adc_bits': ADC_BITS, 'adc_max': ADC_MAX, 'window_s': window,
+            'rounds': rounds,
+            'xbar_ms': round(sec['xbar'] * 1e3, 4),
+            'unblocked_ms': round(sec['unblocked'] * 1e3, 4),
+            'eager_ms': round(sec['eager'] * 1e3, 4),
+            'xbar_over_unblocked': round(sec['xbar'] / sec['unblocked'], 3),
+            'eager_over_xbar': round(sec['eager'] / sec['xbar'], 2),
+            'rounds_ms': {k: [round(t * 1e3, 4) for t in v]
+                          for k, v in rr.items()},
+            'noise_off_outputs_off_by_a_step_vs_eager': moved,
+        }
+        print(json.dumps(res), flush=True)
+        results.append(res)
+    return results
+
+
+def resource_usage():
+    """VGPRs / LDS / scratch of every xbar_fwd_kernel instantiation, from the
+    compiler's own remarks (device-only compile for gfx950, no GPU needed)."""
+    from torch.utils import cpp_extension as ce
+    import sysconfig
+    src = os.path.join(REPO, 'csrc', 'conv_mfma.hip')
+    inc = ['-I' + p for p in ce.include_paths(device_type='cuda')]
+    inc.append('-I' + sysconfig.get_paths()['include'])
+    cmd = ['hipcc', '-c', src, '-o', os.devnull, '-O3', '-std=c++17',
+           '--offload-arch=gfx950', '--offload-device-only',
+           '-D__HIP_PLATFORM_AMD__=1', '-DUSE_ROCM=1', '-DTORCH_HIP=1',
+           '-DTORCH_EXTENSION_NAME=noisynet_hip', '-fno-gpu-rdc',
+           '-mllvm', '--amdgpu-mfma-vgpr-form', '-x', 'hip',
+           '-Rpass-analysis=kernel-resource-usage'] + inc
+    text = subprocess.run(cmd, stderr=subprocess.PIPE, text=True,
+                          check=True).stderr
+    return parse_resource_usage(text)
+
+
+def parse_resource_usage(text):
+    rows, cur = [], None
+    for line in text.splitlines():
+        m = re.search(r'Function Name: (\S+)', line)
+        if m:
+            cur = {'kernel': m.group(1)} if 'xbar_fwd_kernel' in m.group(1) \
+                else None
+            if cur is not None:
+                rows.append(cur)
+            continue
+        if cur is None:
+            continue
+        m = re.search(r'remark:\s+(TotalSGPRs|VGPRs|AGPRs|ScratchSize '
+                      r'\[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|'
+                      r'VGPRs Spill|LDS Size \[bytes/block\]): (\d+)', line)
+        if m:
+            cur[m.group(1)] = int(m.group(2))
+    for r in rows:
+        print(json.dumps(r))
+    # the dynamic LDS tiles are sized at launch: (64 + 3*64) rows of 80 B
+    # (16-bit) or 144 B (fp32), on top of the static bytes reported above
+    print(json.dumps({
+        'kernels': len(rows),
+        'max_VGPRs': max(r['VGPRs'] for r in rows),
+        'max_AGPRs': max(r['AGPRs'] for r in rows),
+        'max_scratch_bytes_per_lane':
+            max(r['ScratchSize [bytes/lane]'] for r in rows),
+        'max_VGPR_spill': max(r['VGPRs Spill'] for r in rows),
+        'min_occupancy_waves_per_simd':
+            min(r['Occupancy [waves/SIMD]'] for r in rows),
+        'max_static_LDS_bytes': max(r['LDS Size [bytes/block]'] for r in rows),
+        'dynamic_LDS_bytes': {'bf16/fp16': 256 * 80, 'fp32': 256 * 144}}))
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--rows', type=int, nargs='+', default=[64, 128, 256])
+    ap.add_argument('--layers', nargs='+', default=list(LAYERS),
+                    choices=list(LAYERS))
+    ap.add_argument('--window', type=float, default=0.3)
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--reps', type=int, default=10,
+                    help='fused calls per timed event pair')
+    ap.add_argument('--resource-usage', action='store_true')
+    args = ap.parse_args()
+    if args.resource_usage:
+        resource_usage()
+        return
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_xbar needs a GPU: nothing measured')
+    slower = []
+    for name in args.layers:
+        for r in bench_layer(name, LAYERS[name], args.rows, args.window,
+                             args.rounds, args.reps):
+            if not r['xbar_ms'] < r['eager_ms']:
+                slower.append((name, r['xbar_rows']))
+    if slower:
+        raise SystemExit('fused op not faster than the eager composition at '
+                         '%s' % slower)
+
+
+if __name__ == '__main__':
+    main()
