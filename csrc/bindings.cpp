@@ -164,6 +164,15 @@ std::vector<torch::Tensor> xbar_fwd_linear(
     torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
     int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
     int64_t adc_bits, torch::Tensor adc, int64_t seed, bool telem);
+std::vector<torch::Tensor> xbar_diff_fwd_conv(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
+    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
+    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t seed,
+    bool telem);
+std::vector<torch::Tensor> xbar_diff_fwd_linear(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
+    int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
+    int64_t adc_bits, torch::Tensor adc, int64_t seed, bool telem);
 
 std::string conv_fused_route(int64_t C, int64_t H, int64_t W, int64_t K,
                              int64_t R, int64_t S, int64_t stride, int64_t pad,
@@ -230,4 +239,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sigma_noise_linear", &sigma_noise_linear_impl);
   m.def("xbar_fwd_conv", &xbar_fwd_conv);
   m.def("xbar_fwd_linear", &xbar_fwd_linear);
+  m.def("xbar_diff_fwd_conv", &xbar_diff_fwd_conv);
+  m.def("xbar_diff_fwd_linear", &xbar_diff_fwd_linear);
 }

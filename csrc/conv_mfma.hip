@@ -3518,6 +3518,274 @@ void xbar_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Differential columns: the positive and the negative part of the weights sit
+// on two columns, each with its own non-negative current, its own noise draw
+// and its own UNIPOLAR ADC; the two codes are subtracted digitally.
+//   wq+ = max(wq, 0)   wq- = max(-wq, 0)     f+- = f(|w_raw|) by sign(w_raw)
+//   p+- = sum x * wq+-                       s+- = max(sum x * f+-, 0)
+//   v+- = p+- + eps+- * sqrt(factor * s+-)
+//   q+- = step * clamp(rint(v+- * inv_step), 0, Qu)
+//   out = sum_b (q+ - q-) + bias
+// The split happens once per staged element, from the one wq and the one
+// w_raw load, into four weight tiles (wq+, wq-, f+, f-): LDS is (64 + 4*64)
+// rows, + 64 for |w_raw| (telemetry with abs2). Splitting the loaded
+// fragments in registers instead would repeat the work in every wave and for
+// every k-step fragment, and gfx950 has no packed bf16 max. The positive
+// column of block b keeps the counter (b*M + m)*K + k, the negative column
+// uses ((nblocks + b)*M + m)*K + k: with weights >= 0 and the ADC off this
+// kernel draws and returns what xbar_fwd_kernel returns. Bias is a run-time
+// branch here (bias == nullptr) to halve the instantiation count.
+// ---------------------------------------------------------------------------
+
+template <typename T, int SIGMA_MODE, bool TELEM>
+DEV_INLINE void xbar_diff_store_tiles(char* a_lds, char* bp_lds, char* bn_lds,
+                                      char* cp_lds, char* cn_lds, char* d_lds,
+                                      const XbarRegs<T>& rg) {
+  int row = threadIdx.x >> 2;
+  int seg = threadIdx.x & 3;
+  xbar_put8<T>(a_lds, row, seg, rg.x);
+  float p[8], n[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float q = to_f32(rg.q[j]);
+    p[j] = fmaxf(q, 0.0f);
+    n[j] = fmaxf(-q, 0.0f);
+  }
+  Mma<T>::store8(bp_lds, row, seg * 8, p);
+  Mma<T>::store8(bn_lds, row, seg * 8, n);
+  if (SIGMA_MODE > 0) {
+    float a[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float w = to_f32(rg.w[j]);
+      a[j] = fabsf(w);
+      float v = (SIGMA_MODE == 2) ? a[j] * a[j] + a[j] : a[j];
+      p[j] = (w > 0.0f) ? v : 0.0f;
+      n[j] = (w < 0.0f) ? v : 0.0f;
+    }
+    Mma<T>::store8(cp_lds, row, seg * 8, p);
+    Mma<T>::store8(cn_lds, row, seg * 8, n);
+    if (TELEM && SIGMA_MODE == 2) Mma<T>::store8(d_lds, row, seg * 8, a);
+  }
+}
+
+// TELEM as in xbar_fwd_kernel, per column: telem[1] sums
+// |sum_b (noise+ - noise-)|, sat_count counts column partials with
+// rint(v / step) > Qu or < 0, telem[4] is the max |v+-|; qu = 2^bits - 1
+template <typename T, int SIGMA_MODE, bool ADC, bool TELEM>
+__global__ __launch_bounds__(kBlock)
+void xbar_diff_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
+                          const T* __restrict__ wraw,
+                          const float* __restrict__ bias, T* __restrict__ out,
+                          ConvGeom g, int wpitch, int xbar_rows,
+                          const float* __restrict__ factor_p,
+                          const float* __restrict__ adc_p /* step, 1/step */,
+                          float qu, uint64_t seed, float* __restrict__ telem,
+                          unsigned long long* __restrict__ sat_count,
+                          const int64_t* __restrict__ seed_base) {
+  seed = graph_seed(seed_base, seed);
+  const float factor = (SIGMA_MODE > 0) ? factor_p[0] : 0.0f;
+  const float step = ADC ? adc_p[0] : 1.0f;
+  const float inv_step = ADC ? adc_p[1] : 1.0f;
+  int n0 = blockIdx.x * BN;
+  int64_t m0 = (int64_t)blockIdx.y * BM;
+
+  constexpr int STR = Mma<T>::STRIDE;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* a_lds = smem;                          // BM rows (x)
+  char* bp_lds = smem + BM * STR;              // BN rows (wq+)
+  char* bn_lds = smem + (BM + BN) * STR;       // BN rows (wq-)
+  char* cp_lds = smem + (BM + 2 * BN) * STR;   // BN rows (f+)
+  char* cn_lds = smem + (BM + 3 * BN) * STR;   // BN rows (f-)
+  char* d_lds = smem + (BM + 4 * BN) * STR;    // BN rows (|w_raw|, telem)
+
+  int wid = threadIdx.x / WAVE;
+  int wm = wid >> 1, wn = wid & 1;
+  int lane = threadIdx.x & (WAVE - 1);
+
+  XbarRow xr;
+  {
+    int64_t sm = m0 + (threadIdx.x >> 2);
+    xr.live = sm < g.M;
+    int oh = 0, ow = 0;
+    xr.img = 0;
+    if (xr.live) {
+      int64_t t = sm;
+      ow = (int)(t % g.OW); t /= g.OW;
+      oh = (int)(t % g.OH); t /= g.OH;
+      xr.img = (int)t;
+    }
+    xr.ih0 = oh * g.stride - g.pad;
+    xr.iw0 = ow * g.stride - g.pad;
+    xr.r = xr.s = xr.c = 0;
+    xbar_row_advance(xr, g, (threadIdx.x & 3) * 8);
+  }
+
+  f32x4 accp[2][2] = {}, accn[2][2] = {};     // p+, p-
+  f32x4 saccp[2][2] = {}, saccn[2][2] = {};   // s+, s-
+  f32x4 tacc[2][2] = {};    // sigma_abs of the block (telemetry, abs2)
+  f32x4 oacc[2][2] = {};    // sum_b (q+ - q-)
+  f32x4 ycl[2][2] = {};     // sum_b (p+ - p-) (telemetry)
+  f32x4 ntot[2][2] = {};    // sum_b (noise+ - noise-) (telemetry)
+  float t_sum_sigma = 0.0f, t_sat = 0.0f, t_vmax = 0.0f;
+
+  const int nrows = g.R * g.S * g.C;
+  const int nblocks = (nrows + xbar_rows - 1) / xbar_rows;
+  const int steps_per_block = xbar_rows / BK;
+  int steps_left = steps_per_block;
+  int b = 0;
+  XbarRegs<T> rg;
+  xbar_load_x(rg.x, x, g, xr);
+  xbar_load_w<T, SIGMA_MODE>(rg.q, rg.w, wq, wraw, g.K, n0, 0, nrows, wpitch);
+  for (int ck = 0; ck < nrows; ck += BK) {
+    xbar_diff_store_tiles<T, SIGMA_MODE, TELEM>(a_lds, bp_lds, bn_lds, cp_lds,
+                                                cn_lds, d_lds, rg);
+    __syncthreads();
+    if (ck + BK < nrows) {  // next step's loads, in flight under the MFMAs
+      xbar_row_advance(xr, g, BK);
+      xbar_load_x(rg.x, x, g, xr);
+      xbar_load_w<T, SIGMA_MODE>(rg.q, rg.w, wq, wraw, g.K, n0, ck + BK,
+                                 nrows, wpitch);
+    }
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm) {
+      auto a = Mma<T>::load(a_lds, wm * 32 + fm * 16 + (lane & 15), lane);
+#pragma unroll
+      for (int fn = 0; fn < 2; ++fn) {
+        int brow = wn * 32 + fn * 16 + (lane & 15);
+        auto bqp = Mma<T>::load(bp_lds, brow, lane);
+        Mma<T>::mma(a, bqp, accp[fm][fn]);
+        auto bqn = Mma<T>::load(bn_lds, brow, lane);
+        Mma<T>::mma(a, bqn, accn[fm][fn]);
+        if (SIGMA_MODE > 0) {
+          auto bsp = Mma<T>::load(cp_lds, brow, lane);
+          Mma<T>::mma(a, bsp, saccp[fm][fn]);
+          auto bsn = Mma<T>::load(cn_lds, brow, lane);
+          Mma<T>::mma(a, bsn, saccn[fm][fn]);
+        }
+        if (TELEM && SIGMA_MODE == 2) {
+          auto bt = Mma<T>::load(d_lds, brow, lane);
+          Mma<T>::mma(a, bt, tacc[fm][fn]);
+        }
+      }
+    }
+    __syncthreads();
+
+    if (--steps_left > 0 && ck + BK < nrows) continue;
+    // block boundary (or the end): noise + ADC on both columns' fragments
+    steps_left = steps_per_block;
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm) {
+#pragma unroll
+      for (int fn = 0; fn < 2; ++fn) {
+        int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
+        int n = n0 + wn * 32 + fn * 16 + (lane & 15);
+        float gp[4], gn[4];
+        if (SIGMA_MODE > 0) {
+          gauss4(seed, (uint64_t)(((int64_t)b * g.M + mb) * g.K + n), gp);
+          gauss4(seed,
+                 (uint64_t)(((int64_t)(nblocks + b) * g.M + mb) * g.K + n), gn);
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          bool inside = mb + reg < g.M && n < g.K;
+          float pp = accp[fm][fn][reg], pn = accn[fm][fn][reg];
+          float vp = pp, vn = pn;
+          if (SIGMA_MODE > 0) {
+            float sp = fmaxf(saccp[fm][fn][reg], 0.0f);
+            float sn = fmaxf(saccn[fm][fn][reg], 0.0f);
+            float noisep = gp[reg] * sqrtf(factor * sp);
+            float noisen = gn[reg] * sqrtf(factor * sn);
+            vp = pp + noisep;
+            vn = pn + noisen;
+            if (TELEM) {
+              ntot[fm][fn][reg] += noisep - noisen;
+              if (inside)
+                t_sum_sigma += (SIGMA_MODE == 2)
+                                   ? tacc[fm][fn][reg]
+                                   : saccp[fm][fn][reg] + saccn[fm][fn][reg];
+            }
+          }
+          float qp = vp, qn = vn;
+          if (ADC) {
+            float tp = rintf(vp * inv_step);
+            float tn = rintf(vn * inv_step);
+            if (TELEM && inside) {
+              if (tp > qu || tp < 0.0f) t_sat += 1.0f;
+              if (tn > qu || tn < 0.0f) t_sat += 1.0f;
+            }
+            qp = step * fminf(fmaxf(tp, 0.0f), qu);
+            qn = step * fminf(fmaxf(tn, 0.0f), qu);
+          }
+          if (TELEM) {
+            ycl[fm][fn][reg] += pp - pn;
+            if (inside)
+              t_vmax = fmaxf(t_vmax, fmaxf(fabsf(vp), fabsf(vn)));
+          }
+          oacc[fm][fn][reg] += qp - qn;
+        }
+        accp[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        accn[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        saccp[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        saccn[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        tacc[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      }
+    }
+    ++b;
+  }
+
+  // bias, the one rounding to the dtype, stores
+  float t_sum_noise = 0.0f, t_max_y = -INFINITY;
+#pragma unroll
+  for (int fm = 0; fm < 2; ++fm) {
+#pragma unroll
+    for (int fn = 0; fn < 2; ++fn) {
+      int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
+      int n = n0 + wn * 32 + fn * 16 + (lane & 15);
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        int64_t m = mb + reg;
+        if (m < g.M && n < g.K) {
+          float bv = bias ? bias[n] : 0.0f;
+          out[m * g.K + n] = from_f32<T>(oacc[fm][fn][reg] + bv);
+          if (TELEM) {
+            t_sum_noise += fabsf(ntot[fm][fn][reg]);
+            t_max_y = fmaxf(t_max_y, ycl[fm][fn][reg] + bv);
+          }
+        }
+      }
+    }
+  }
+  if (TELEM) {
+    __shared__ float red[4];
+    __shared__ float redm[2][4];
+    float s0 = block_sum(t_sum_sigma, red);
+    __syncthreads();
+    float s1 = block_sum(t_sum_noise, red);
+    __syncthreads();
+    float s3 = block_sum(t_sat, red);  // <= 8192 per epilogue: exact
+    float my = wave_max(t_max_y);
+    float mv = wave_max(t_vmax);
+    if (lane == 0) {
+      redm[0][wid] = my;
+      redm[1][wid] = mv;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      if (SIGMA_MODE > 0) {
+        atomicAdd(&telem[0], s0);
+        atomicAdd(&telem[1], s1);
+      }
+      atomic_max_f32(&telem[2], fmaxf(fmaxf(redm[0][0], redm[0][1]),
+                                      fmaxf(redm[0][2], redm[0][3])));
+      if (ADC) atomicAdd(sat_count, (unsigned long long)(s3 + 0.5f));
+      atomic_max_f32(&telem[4], fmaxf(fmaxf(redm[1][0], redm[1][1]),
+                                      fmaxf(redm[1][2], redm[1][3])));
+    }
+  }
+}
+
 void check_xbar_args(int64_t sigma_mode, int64_t xbar_rows, int64_t adc_bits,
                      const torch::Tensor& adc, const torch::Tensor& x,
                      const char* who) {
@@ -3542,7 +3810,7 @@ std::vector<torch::Tensor> xbar_fwd_impl(
     const torch::Tensor& bias, ConvGeom g, torch::Tensor out,
     int64_t sigma_mode, const torch::Tensor& factor, int64_t xbar_rows,
     int64_t adc_bits, const torch::Tensor& adc, int64_t seed, bool telem,
-    const char* who) {
+    bool diff, const char* who) {
   check_xbar_args(sigma_mode, xbar_rows, adc_bits, adc, x, who);
   int nrows = g.R * g.S * g.C;
   TORCH_CHECK(wq2.dim() == 2 && wq2.size(0) == g.K && wq2.size(1) == nrows &&
@@ -3577,11 +3845,14 @@ std::vector<torch::Tensor> xbar_fwd_impl(
   }
   auto factor_f = factor.to(torch::kFloat32).reshape({1}).contiguous();
   bool adc_on = adc_bits > 0;
-  float qm = adc_on ? (float)((1 << (adc_bits - 1)) - 1) : 0.0f;
+  // top ADC code: bipolar +-Qm, or unipolar 0..Qu on differential columns
+  float qm = !adc_on ? 0.0f
+             : diff  ? (float)((1 << adc_bits) - 1)
+                     : (float)((1 << (adc_bits - 1)) - 1);
   dim3 grid((g.K + BN - 1) / BN, (int)((g.M + BM - 1) / BM));
   NN_DISPATCH(x.scalar_type(), "xbar_fwd", [&] {
     using T = typename DevT<scalar_t>::type;
-    size_t lds = (size_t)(BM + 3 * BN) * Mma<T>::STRIDE;
+    size_t lds = (size_t)(BM + (diff ? 5 : 3) * BN) * Mma<T>::STRIDE;
     auto stream = c10::hip::getCurrentHIPStream();
     const T* xp = (const T*)x.data_ptr();
     const T* wqp = (const T*)wq2.data_ptr();
@@ -3605,8 +3876,18 @@ std::vector<torch::Tensor> xbar_fwd_impl(
     auto with_bias = [&](auto sm, auto ad, auto tl) {
       if (has_bias) launch(sm, ad, tl, TT{}); else launch(sm, ad, tl, FF{});
     };
+    auto launch_diff = [&](auto sm, auto ad, auto tl) {
+      hipLaunchKernelGGL((xbar_diff_fwd_kernel<T, decltype(sm)::value,
+                          decltype(ad)::value, decltype(tl)::value>), grid,
+                         dim3(kBlock), lds, stream, xp, wqp, wrp, bp, op, g,
+                         pitch, (int)xbar_rows, f, ap, qm, sd, tp, sp,
+                         g_seed_base);
+    };
+    auto with_route = [&](auto sm, auto ad, auto tl) {
+      if (diff) launch_diff(sm, ad, tl); else with_bias(sm, ad, tl);
+    };
     auto with_telem = [&](auto sm, auto ad) {
-      if (telem) with_bias(sm, ad, TT{}); else with_bias(sm, ad, FF{});
+      if (telem) with_route(sm, ad, TT{}); else with_route(sm, ad, FF{});
     };
     auto with_adc = [&](auto sm) {
       if (adc_on) with_telem(sm, TT{}); else with_telem(sm, FF{});
@@ -3621,21 +3902,21 @@ std::vector<torch::Tensor> xbar_fwd_impl(
   return {out, tele};
 }
 
-}  // namespace
-
-std::vector<torch::Tensor> xbar_fwd_conv(
-    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
-    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
-    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t seed,
-    bool telem) {
-  check_cl(x, "xbar_fwd_conv x");
-  check_cl(wq, "xbar_fwd_conv wq");
-  check_cl(wraw, "xbar_fwd_conv wraw");
-  TORCH_CHECK(wq.size(1) == x.size(1), "xbar_fwd_conv: channel mismatch");
+std::vector<torch::Tensor> xbar_conv_entry(
+    const torch::Tensor& x, const torch::Tensor& wq, const torch::Tensor& wraw,
+    const torch::Tensor& bias, int64_t stride, int64_t pad, int64_t sigma_mode,
+    const torch::Tensor& factor, int64_t xbar_rows, int64_t adc_bits,
+    const torch::Tensor& adc, int64_t seed, bool telem, bool diff,
+    const char* who) {
+  const std::string name(who);
+  check_cl(x, (name + " x").c_str());
+  check_cl(wq, (name + " wq").c_str());
+  check_cl(wraw, (name + " wraw").c_str());
+  TORCH_CHECK(wq.size(1) == x.size(1), who, ": channel mismatch");
   auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
                      (int)x.size(1), (int)wq.size(0), (int)wq.size(2),
                      (int)wq.size(3), (int)stride, (int)pad);
-  TORCH_CHECK(g.OH > 0 && g.OW > 0, "xbar_fwd_conv: empty output");
+  TORCH_CHECK(g.OH > 0 && g.OW > 0, who, ": empty output");
   auto out = torch::empty({g.N, g.K, g.OH, g.OW},
                           x.options().memory_format(at::MemoryFormat::ChannelsLast));
   int64_t nrows = (int64_t)g.R * g.S * g.C;
@@ -3646,18 +3927,60 @@ std::vector<torch::Tensor> xbar_fwd_conv(
   auto wq2 = rows(wq);
   auto wr2 = wraw.is_same(wq) ? wq2 : rows(wraw);
   return xbar_fwd_impl(x, wq2, wr2, bias, g, out, sigma_mode, factor,
-                       xbar_rows, adc_bits, adc, seed, telem, "xbar_fwd_conv");
+                       xbar_rows, adc_bits, adc, seed, telem, diff, who);
+}
+
+std::vector<torch::Tensor> xbar_linear_entry(
+    const torch::Tensor& x, const torch::Tensor& wq, const torch::Tensor& wraw,
+    const torch::Tensor& bias, int64_t sigma_mode, const torch::Tensor& factor,
+    int64_t xbar_rows, int64_t adc_bits, const torch::Tensor& adc,
+    int64_t seed, bool telem, bool diff, const char* who) {
+  TORCH_CHECK(wq.dim() == 2 && wq.size(1) == x.size(1), who,
+              ": weight shape mismatch");
+  auto g = linear_geom(x, wq.size(0));
+  auto out = torch::empty({x.size(0), wq.size(0)}, x.options());
+  return xbar_fwd_impl(x, wq, wraw, bias, g, out, sigma_mode, factor,
+                       xbar_rows, adc_bits, adc, seed, telem, diff, who);
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> xbar_fwd_conv(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
+    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
+    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t seed,
+    bool telem) {
+  return xbar_conv_entry(x, wq, wraw, bias, stride, pad, sigma_mode, factor,
+                         xbar_rows, adc_bits, adc, seed, telem, false,
+                         "xbar_fwd_conv");
 }
 
 std::vector<torch::Tensor> xbar_fwd_linear(
     torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
     int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
     int64_t adc_bits, torch::Tensor adc, int64_t seed, bool telem) {
-  TORCH_CHECK(wq.dim() == 2 && wq.size(1) == x.size(1),
-              "xbar_fwd_linear: weight shape mismatch");
-  auto g = linear_geom(x, wq.size(0));
-  auto out = torch::empty({x.size(0), wq.size(0)}, x.options());
-  return xbar_fwd_impl(x, wq, wraw, bias, g, out, sigma_mode, factor,
-                       xbar_rows, adc_bits, adc, seed, telem,
-                       "xbar_fwd_linear");
+  return xbar_linear_entry(x, wq, wraw, bias, sigma_mode, factor, xbar_rows,
+                           adc_bits, adc, seed, telem, false,
+                           "xbar_fwd_linear");
+}
+
+// differential columns (W+ / W- with unipolar per-column ADCs): same
+// arguments; adc is [step, 1/step] of the unipolar step adc_max / (2^bits - 1)
+std::vector<torch::Tensor> xbar_diff_fwd_conv(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
+    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
+    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t seed,
+    bool telem) {
+  return xbar_conv_entry(x, wq, wraw, bias, stride, pad, sigma_mode, factor,
+                         xbar_rows, adc_bits, adc, seed, telem, true,
+                         "xbar_diff_fwd_conv");
+}
+
+std::vector<torch::Tensor> xbar_diff_fwd_linear(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
+    int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
+    int64_t adc_bits, torch::Tensor adc, int64_t seed, bool telem) {
+  return xbar_linear_entry(x, wq, wraw, bias, sigma_mode, factor, xbar_rows,
+                           adc_bits, adc, seed, telem, true,
+                           "xbar_diff_fwd_linear");
 }

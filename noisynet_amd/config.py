@@ -114,6 +114,11 @@ def build_noisynet_parser():
     for i in (1, 2, 3, 4):
         parser.add_argument('--adc_max%d' % i, type=float, default=0.0,
                             metavar='')
+    parser.add_argument('--xbar_diff', action='store_true',
+                        help='differential columns: W+ and W- on two columns '
+                             'per tile, each with its own noise and a '
+                             'unipolar ADC over [0, adc_max] (needs '
+                             '--xbar_rows)')
     return parser
 
 

@@ -348,18 +348,24 @@ def train_one(args, model, train_inputs, train_labels, test_inputs, test_labels,
 def print_xbar_stats(model, args):
     """Per-layer tile statistics of the epoch's first 20 batches: power and
     NSR of the noisy layers, the share of tile partial sums the ADC clipped,
-    and max |tile partial| -- the figure to pick --adc_max from."""
+    and max |tile partial| -- the figure to pick --adc_max from. With
+    --xbar_diff the clip share and the max are per column partial (W+ and W-
+    columns, unipolar ADCs)."""
     def mean(v):
         return float(np.mean(v)) if len(v) else float('nan')
 
+    diff = getattr(args, 'xbar_diff', False)
+    adc_kind = ('differential columns, unipolar ADC, ' if diff else '')
+    clip_name = 'clipped per column' if diff else 'clipped'
     for k in range(args.num_layers):
         if not model.partial_absmax[k]:
             continue
-        print('\txbar layer {:d} ({:d} rows/tile, {:d}-bit ADC, adc_max {:g}):'
-              '  power {:.3g}  NSR {:.3g}  clipped {:.2%}  max|partial| {:.4g}'
-              .format(k + 1, args.xbar_rows, args.q_adc,
+        print('\txbar layer {:d} ({:d} rows/tile, {}{:d}-bit ADC, '
+              'adc_max {:g}):  power {:.3g}  NSR {:.3g}  {} {:.2%}  '
+              'max|partial| {:.4g}'
+              .format(k + 1, args.xbar_rows, adc_kind, args.q_adc,
                       getattr(args, 'adc_max%d' % (k + 1)),
-                      mean(model.power[k]), mean(model.nsr[k]),
+                      mean(model.power[k]), mean(model.nsr[k]), clip_name,
                       mean(model.adc_clip[k]),
                       max(model.partial_absmax[k])))
 

@@ -32,7 +32,10 @@ and its own ADC (--q_adc bits over +-adc_max), through ops.xbar_noisy_conv2d /
 xbar_noisy_linear on the hot path. The conv1+pool kernel is bypassed, the
 introspective flags are refused (ValueError), and ``model.adc_clip`` /
 ``model.partial_absmax`` collect the first 20 batches' ADC statistics next to
-power / nsr. With --xbar_rows 0 nothing changes.
+power / nsr. With --xbar_rows 0 nothing changes. --xbar_diff puts W+ and W- of
+every tile on two columns, each with its own noise and a unipolar ADC over
+[0, adc_max] (ops.xbar_noisy_*(..., differential=True)); ``adc_clip`` is then
+the share of clipped COLUMN partials. It needs --xbar_rows.
 """
 
 import torch
@@ -111,6 +114,10 @@ class Net(nn.Module):
         self.adc_clip = [[] for _ in range(args.num_layers)]
         self.partial_absmax = [[] for _ in range(args.num_layers)]
         self.xbar_rows = getattr(args, 'xbar_rows', 0) or 0
+        self.xbar_diff = bool(getattr(args, 'xbar_diff', False))
+        if self.xbar_diff and self.xbar_rows <= 0:
+            raise ValueError('--xbar_diff needs --xbar_rows > 0: differential '
+                             'columns are a mode of the tiled crossbars')
         if self.xbar_rows > 0:
             self._check_xbar_args()
 
@@ -202,7 +209,8 @@ class Net(nn.Module):
                     is_conv):
         """The layer on tiled crossbars: per-tile noise when its current is
         > 0 and per-tile ADC when --q_adc > 0 (ops.xbar_noisy_*). A layer with
-        neither is the plain layer, which tiling does not change."""
+        neither is the plain layer, which tiling does not change. With
+        --xbar_diff every tile runs on differential columns."""
         a = self.args
         q_adc = getattr(a, 'q_adc', 0) or 0
         if current <= 0 and q_adc == 0:
@@ -231,13 +239,13 @@ class Net(nn.Module):
                 x, wq, w_raw.detach(), bias, 1, 0, sigma_mode, factor,
                 self.xbar_rows, q_adc, adc_max, current=current,
                 power_denom=power_denom, want_telemetry=want_telemetry,
-                telemetry_out=telem)
+                telemetry_out=telem, differential=self.xbar_diff)
         else:
             out = ops.xbar_noisy_linear(
                 x, wq, w_raw.detach(), bias, sigma_mode, factor,
                 self.xbar_rows, q_adc, adc_max, current=current,
                 power_denom=power_denom, want_telemetry=want_telemetry,
-                telemetry_out=telem)
+                telemetry_out=telem, differential=self.xbar_diff)
         if want_telemetry:
             if telem.power is not None:
                 self.power[layer_num].append(float(telem.power))

@@ -608,7 +608,12 @@ class XbarTelemetry(NoiseTelemetry):
     """NoiseTelemetry of a tiled-crossbar call plus the ADC statistics:
     ``adc_clip_share`` (share of block partials beyond the ADC range) and
     ``partial_absmax`` (max |v_b| over every block partial -- the value to
-    pick ``adc_max`` from). power / nsr stay None when the noise is off."""
+    pick ``adc_max`` from). power / nsr stay None when the noise is off.
+
+    With differential columns both figures are per COLUMN partial: the share
+    is over the 2 * nblocks * M * K column values v+ / v- (beyond the top code
+    or below zero), ``partial_absmax`` is the max |v+-|, and nsr uses the
+    digital difference of the two columns' noises."""
 
     __slots__ = ("adc_clip_share", "partial_absmax")
 
@@ -624,14 +629,21 @@ _XBAR_MODE = {None: 0, "abs": 1, "abs2": 2}
 
 def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
                   sigma_mode, factor, xbar_rows, adc_bits, adc_max,
-                  want_telemetry):
+                  want_telemetry, differential=False):
     """Shared forward of the two xbar Functions. Returns (y, tele) with tele a
     dict of 0-dim tensors (or None): sigma_abs, abs_noise, max_y, clipped,
-    n_partials, partial_absmax -- sums over the whole call."""
+    n_partials, partial_absmax -- sums over the whole call. ``differential``
+    runs W+ / W- columns with unipolar ADCs (two partials per block)."""
     x = x2_or_x
-    adc = ref.xbar_adc_params(adc_bits, adc_max, x.device)
+    differential = bool(differential)
+    adc = ref.xbar_adc_params(adc_bits, adc_max, x.device,
+                              unipolar=differential)
     n_rows = wq[0].numel()
     nblocks = -(-n_rows // int(xbar_rows))
+    if differential:
+        fwd_conv, fwd_linear = "xbar_diff_fwd_conv", "xbar_diff_fwd_linear"
+    else:
+        fwd_conv, fwd_linear = "xbar_fwd_conv", "xbar_fwd_linear"
     if use_native(x, wq):
         empty = torch.empty(0, device=x.device, dtype=x.dtype)
         empty_f = torch.empty(0, device=x.device, dtype=torch.float32)
@@ -643,17 +655,19 @@ def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
                   _next_seed(x.device), bool(want_telemetry))
         wr = w_raw if sigma_mode is not None else wq
         if is_conv:
-            y, t = ext().xbar_fwd_conv(
+            y, t = getattr(ext(), fwd_conv)(
                 _nhwc(x), _nhwc(wq), _nhwc(wr),
                 bias if bias is not None else empty, stride, padding, *common)
         else:
-            y, t = ext().xbar_fwd_linear(
+            y, t = getattr(ext(), fwd_linear)(
                 x.contiguous(), wq.contiguous(), wr.contiguous(),
                 bias if bias is not None else empty, *common)
         tele = None
         if want_telemetry:
             tele = dict(sigma_abs=t[0], abs_noise=t[1], max_y=t[2],
-                        clipped=t[3], n_partials=nblocks * y.numel(),
+                        clipped=t[3],
+                        n_partials=(2 if differential else 1) * nblocks
+                        * y.numel(),
                         partial_absmax=t[4])
         return y, tele
     tele = {} if want_telemetry else None
@@ -669,7 +683,8 @@ def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
             ref.xbar_weight_rows(w_raw.detach()) if sigma_mode is not None
             else None,
             bias.detach() if bias is not None else None, sigma_mode, factor,
-            int(xbar_rows), adc_bits, adc, stats=tele)
+            int(xbar_rows), adc_bits, adc, stats=tele,
+            differential=differential)
         if is_conv:
             N, K = x.shape[0], wq.shape[0]
             oh = (x.shape[2] + 2 * padding - R) // stride + 1
@@ -698,17 +713,19 @@ class _XbarNoisyConv(torch.autograd.Function):
     """Tiled-crossbar conv: per-block noise + ADC fused into one MFMA pass
     (xbar_fwd_kernel, csrc/conv_mfma.hip). Backward is the identity straight-through over the
     noise and the ADC: exactly the gradients of the unblocked conv with wq.
-    A clipped STE would need per-block saturation masks and is not built."""
+    A clipped STE would need per-block saturation masks and is not built.
+    ``differential`` selects xbar_diff_fwd_kernel (W+ / W- columns, unipolar
+    ADCs); the backward is the same."""
 
     @staticmethod
     def forward(ctx, x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
                 xbar_rows, adc_bits, adc_max, want_telemetry, telemetry_out,
-                current, power_denom):
+                current, power_denom, differential=False):
         ctx.stride, ctx.padding = stride, padding
         ctx.has_bias = bias is not None
         y, tele = _xbar_forward(x, True, wq, w_raw, bias, stride, padding,
                                 sigma_mode, factor, xbar_rows, adc_bits,
-                                adc_max, want_telemetry)
+                                adc_max, want_telemetry, differential)
         if want_telemetry and telemetry_out is not None:
             _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
                           power_denom)
@@ -725,7 +742,7 @@ class _XbarNoisyConv(torch.autograd.Function):
             gw = ConvWgrad.apply(g, x, ctx.stride, ctx.padding, wq.shape, None)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum(dim=(0, 2, 3))
-        return (gx, gw, None, gb) + (None,) * 11
+        return (gx, gw, None, gb) + (None,) * 12
 
 
 class _XbarNoisyLinear(torch.autograd.Function):
@@ -734,11 +751,11 @@ class _XbarNoisyLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
                 adc_bits, adc_max, want_telemetry, telemetry_out, current,
-                power_denom):
+                power_denom, differential=False):
         ctx.has_bias = bias is not None
         y, tele = _xbar_forward(x, False, wq, w_raw, bias, 1, 0, sigma_mode,
                                 factor, xbar_rows, adc_bits, adc_max,
-                                want_telemetry)
+                                want_telemetry, differential)
         if want_telemetry and telemetry_out is not None:
             _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
                           power_denom)
@@ -755,13 +772,13 @@ class _XbarNoisyLinear(torch.autograd.Function):
             gw = LinearWgrad.apply(g, x)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum(dim=0)
-        return (gx, gw, None, gb) + (None,) * 9
+        return (gx, gw, None, gb) + (None,) * 10
 
 
 def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
                       xbar_rows, adc_bits, adc_max, current=0.0,
                       power_denom=1.0, want_telemetry=False,
-                      telemetry_out=None):
+                      telemetry_out=None, differential=False):
     """Noisy conv on tiled crossbars.
 
     The contraction index is the filter's memory order (r, s, c), c fastest;
@@ -784,6 +801,22 @@ def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
 
     ``telemetry_out`` (an XbarTelemetry) receives power / nsr / sparsity as
     fused_noisy_conv2d does, plus adc_clip_share and partial_absmax.
+
+    ``differential=True`` puts the positive and the negative part of the
+    weights on two columns, each with its own noise draw and its own unipolar
+    ADC, subtracted digitally. Per block, in fp32,
+        wq+ = max(wq, 0)    wq- = max(-wq, 0)       (by the sign of wq)
+        f+- = f(|w_raw|) where w_raw > 0 / < 0, else 0
+        p+- = sum x*wq+-    s+- = max(sum x*f+-, 0)
+        v+- = p+- + eps+- * sqrt(factor * s+-)      eps+, eps- independent
+        q+- = step * clamp(rint(v+- * (1/step)), 0, Qu)
+    with Qu = 2^adc_bits - 1, step = adc_max / Qu, and
+    out = sum_b (q+ - q-) + bias. A column value that rounds below 0 clamps to
+    0 and counts as clipped. The op does not inspect the sign of x; the mode
+    is meant for non-negative activations (post-ReLU, or images in [0, 1]),
+    where each column carries a non-negative current. The telemetry's ADC
+    figures are then per column partial (2 * nblocks per output). The backward
+    is unchanged.
     """
     if isinstance(stride, (tuple, list)):
         stride = stride[0]
@@ -793,20 +826,23 @@ def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
     return _XbarNoisyConv.apply(x, wq, w_raw, bias, stride, padding,
                                 sigma_mode, factor, xbar_rows, adc_bits,
                                 adc_max, want_telemetry, telemetry_out,
-                                current, power_denom)
+                                current, power_denom, bool(differential))
 
 
 def xbar_noisy_linear(x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
                       adc_bits, adc_max, current=0.0, power_denom=1.0,
-                      want_telemetry=False, telemetry_out=None):
+                      want_telemetry=False, telemetry_out=None,
+                      differential=False):
     """Noisy linear layer on tiled crossbars: xbar_noisy_conv2d with the input
     index as the crossbar row. Same straight-through backward (the gradients
-    of F.linear(x, wq, bias)); a clipped STE is out of scope."""
+    of F.linear(x, wq, bias)); a clipped STE is out of scope.
+    ``differential=True`` selects the W+ / W- columns with unipolar ADCs
+    described there (meant for non-negative activations)."""
     ref.xbar_check_args(sigma_mode, xbar_rows, adc_bits, adc_max)
     return _XbarNoisyLinear.apply(x, wq, w_raw, bias, sigma_mode, factor,
                                   xbar_rows, adc_bits, adc_max,
                                   want_telemetry, telemetry_out, current,
-                                  power_denom)
+                                  power_denom, bool(differential))
 
 
 # ---------------------------------------------------------------------------

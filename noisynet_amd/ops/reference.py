@@ -110,12 +110,17 @@ def xbar_check_args(sigma_mode, xbar_rows, adc_bits, adc_max):
                          % (adc_max,))
 
 
-def xbar_adc_params(adc_bits, adc_max, device):
+def xbar_adc_params(adc_bits, adc_max, device, unipolar=False):
     """fp32 tensor [step, 1/step] with step = adc_max / Qm, both rounded once
-    to fp32 (the values the kernel multiplies with); None with the ADC off."""
+    to fp32 (the values the kernel multiplies with); None with the ADC off.
+    ``unipolar`` (differential columns): codes 0..Qu, step = adc_max / Qu with
+    Qu = 2^adc_bits - 1."""
     if adc_bits == 0:
         return None
-    qm = float(2 ** (int(adc_bits) - 1) - 1)
+    if unipolar:
+        qm = float(2 ** int(adc_bits) - 1)
+    else:
+        qm = float(2 ** (int(adc_bits) - 1) - 1)
     if isinstance(adc_max, torch.Tensor):
         amax = adc_max.detach().to(device=device, dtype=torch.float32).reshape(1)
     else:
@@ -145,7 +150,7 @@ def xbar_weight_rows(w):
 
 
 def xbar_vmm(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows, adc_bits,
-             adc, gen=None, stats=None):
+             adc, gen=None, stats=None, differential=False):
     """Blocked analog VMM on row matrices: xm [M, n], wqm / wrm [K, n].
 
     Block b covers rows [b*xbar_rows, min((b+1)*xbar_rows, n)). Per block
@@ -157,7 +162,12 @@ def xbar_vmm(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows, adc_bits,
     sigma_mode None = noise off. ``stats`` (a dict) receives the telemetry
     sums: sigma_abs, abs_noise (of the summed block noises), max_y (clean,
     with bias), clipped (count of |rint(v_b/step)| > Qm), n_partials and
-    partial_absmax (max |v_b|). Returns fp32 [M, K]."""
+    partial_absmax (max |v_b|). Returns fp32 [M, K].
+
+    ``differential`` runs every block on two columns (see _xbar_vmm_diff)."""
+    if differential:
+        return _xbar_vmm_diff(xm, wqm, wrm, bias, sigma_mode, factor,
+                              xbar_rows, adc_bits, adc, gen, stats)
     xm, wqm = xm.float(), wqm.float()
     n = xm.shape[1]
     M, K = xm.shape[0], wqm.shape[0]
@@ -210,6 +220,83 @@ def xbar_vmm(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows, adc_bits,
         stats.update(sigma_abs=sig_abs, abs_noise=noise_tot.abs().sum(),
                      max_y=clean.max(), clipped=clipped,
                      n_partials=nblk * M * K, partial_absmax=absmax)
+    return out
+
+
+def _xbar_vmm_diff(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows,
+                   adc_bits, adc, gen=None, stats=None):
+    """xbar_vmm on differential columns: the positive and the negative part of
+    the weights sit on two columns with independent noise and unipolar ADCs.
+        wq+ = max(wq, 0)   wq- = max(-wq, 0)    f+- = f(|w_raw|) by sign(w_raw)
+        p+- = x_b @ wq+-^T                      s+- = max(x_b @ f+-^T, 0)
+        v+- = p+- + eps+- * sqrt(factor * s+-)
+        q+- = step * clamp(rint(v+- * (1/step)), 0, Qu),  Qu = 2^adc_bits - 1
+    and out = sum_b (q+ - q-) + bias. ``stats``: clipped counts column values
+    with rint(v/step) > Qu or < 0, n_partials is 2 * nblocks * M * K,
+    partial_absmax the max |v+-|, abs_noise uses noise+ - noise-. Meant for
+    non-negative x; the sign of x is not inspected."""
+    xm, wqm = xm.float(), wqm.float()
+    n = xm.shape[1]
+    M, K = xm.shape[0], wqm.shape[0]
+    out = torch.zeros(M, K, dtype=torch.float32, device=xm.device)
+    wqs = (wqm.clamp_min(0), (-wqm).clamp_min(0))
+    if sigma_mode is not None:
+        wr = wrm.float()
+        aw = wr.abs()
+        fw = aw * aw + aw if sigma_mode == "abs2" else aw
+        zero = torch.zeros_like(fw)
+        fws = (torch.where(wr > 0, fw, zero), torch.where(wr < 0, fw, zero))
+        factor = torch.as_tensor(factor, dtype=torch.float32, device=xm.device)
+    if adc is not None:
+        step, inv_step = adc[0], adc[1]
+        qu = float(2 ** int(adc_bits) - 1)
+    if stats is not None:
+        clean = torch.zeros_like(out)
+        noise_tot = torch.zeros_like(out)
+        sig_abs = out.new_zeros(())
+        clipped = 0
+        absmax = out.new_zeros(())
+        nblk = 0
+    for k0 in range(0, n, xbar_rows):
+        k1 = min(k0 + xbar_rows, n)
+        xb = xm[:, k0:k1]
+        qs = []
+        for col in range(2):          # the positive column draws first
+            p = xb @ wqs[col][:, k0:k1].t()
+            v = p
+            if sigma_mode is not None:
+                s = (xb @ fws[col][:, k0:k1].t()).clamp_min(0)
+                eps = torch.randn(p.shape, dtype=torch.float32,
+                                  device=p.device, generator=gen)
+                nb = eps * (factor * s).sqrt()
+                v = p + nb
+            if adc is not None:
+                t = torch.round(v * inv_step)
+                q = step * t.clamp(0, qu)
+            else:
+                q = v
+            qs.append(q)
+            if stats is not None:
+                sgn = 1.0 if col == 0 else -1.0
+                clean = clean + sgn * p
+                absmax = torch.maximum(absmax, v.abs().max())
+                if sigma_mode is not None:
+                    noise_tot = noise_tot + sgn * nb
+                if adc is not None:
+                    clipped = clipped + ((t > qu) | (t < 0)).sum()
+        out = out + (qs[0] - qs[1])
+        if stats is not None:
+            nblk += 1
+            if sigma_mode is not None:
+                sig_abs = sig_abs + (xb @ aw[:, k0:k1].t()).sum()
+    if bias is not None:
+        out = out + bias.float()
+    if stats is not None:
+        if bias is not None:
+            clean = clean + bias.float()
+        stats.update(sigma_abs=sig_abs, abs_noise=noise_tot.abs().sum(),
+                     max_y=clean.max(), clipped=clipped,
+                     n_partials=2 * nblk * M * K, partial_absmax=absmax)
     return out
 
 

@@ -15,6 +15,10 @@ and for xbar_rows in {64, 128, 256}:
   (c) eager     what a user would write without (a): im2col once, then per
                 block slice -> two bf16 matmuls -> randn noise -> round /
                 clamp -> add, every partial through memory
+  (d) diff      (a) with differential=True: W+ / W- columns, two noise draws
+                and two unipolar ADCs per block, still one kernel
+  (c') eager_diff  the eager composition of the differential model: four
+                bf16 matmuls per block, twice those of (c)
 
 Device events around windows of at least --window seconds after a warm-up,
 the variants alternating over --rounds rounds in one process; the median
@@ -23,7 +27,7 @@ CPU fallback: a time is a GPU time or it is not reported.
 
 --resource-usage needs no GPU: it compiles csrc/conv_mfma.hip for gfx950 with
 -Rpass-analysis=kernel-resource-usage and prints VGPRs, LDS and scratch of
-every xbar_fwd_kernel instantiation.
+every xbar_fwd_kernel and xbar_diff_fwd_kernel instantiation.
 """
 
 import argparse
@@ -69,6 +73,33 @@ def eager_blocked(xm, wq, fw, factor, xbar_rows, step, inv_step, qm,
     return out
 
 
+def eager_diff(xm, wq, wr, factor, xbar_rows, step, inv_step, qu, mode=MODE,
+               fp32_matmul=False):
+    """The differential model composed of stock torch ops: per block and per
+    column a wq+- matmul, an f+- matmul, randn noise and a unipolar round /
+    clamp; the two columns subtracted, every partial through memory. The
+    split weight matrices are prepared once, outside the timed region."""
+    wqs, fws = wq, wr       # tuples (positive column, negative column)
+    if fp32_matmul:
+        xm = xm.float()
+        wqs = tuple(w.float() for w in wqs)
+        fws = tuple(w.float() for w in fws)
+    n = xm.shape[1]
+    out = None
+    for k0 in range(0, n, xbar_rows):
+        k1 = min(k0 + xbar_rows, n)
+        xb = xm[:, k0:k1]
+        qs = []
+        for col in range(2):
+            p = (xb @ wqs[col][:, k0:k1].t()).float()
+            s = (xb @ fws[col][:, k0:k1].t()).float().clamp_min(0)
+            v = p + torch.randn_like(p) * (factor * s).sqrt()
+            qs.append(step * torch.round(v * inv_step).clamp(0, qu))
+        q = qs[0] - qs[1]
+        out = q if out is None else out + q
+    return out
+
+
 def timed(fn, window, min_calls=3):
     """seconds per call over a window >= ``window``."""
     calls, total = 0, 0.0
@@ -104,6 +135,16 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
     aw = ref.xbar_weight_rows(wr).abs()
     fw_rows = (aw * aw + aw).contiguous()
     n = wq_rows.shape[1]
+    # differential columns: unipolar step, split weight matrices
+    adc_u = ref.xbar_adc_params(ADC_BITS, ADC_MAX, dev, unipolar=True)
+    step_u, inv_step_u = adc_u[0], adc_u[1]
+    qu = float(2 ** ADC_BITS - 1)
+    wq_cols = (wq_rows.clamp_min(0).contiguous(),
+               (-wq_rows).clamp_min(0).contiguous())
+    wr_rows = ref.xbar_weight_rows(wr)
+    zero = torch.zeros_like(fw_rows)
+    fw_cols = (torch.where(wr_rows > 0, fw_rows, zero).contiguous(),
+               torch.where(wr_rows < 0, fw_rows, zero).contiguous())
 
     def run_unblocked():
         for _ in range(reps):
@@ -132,8 +173,28 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
                           qm)
             return 1
 
+        def run_diff():
+            for _ in range(reps):
+                if conv:
+                    ops.xbar_noisy_conv2d(x, wq, wr, None, 1, 0, MODE, factor,
+                                          rows, ADC_BITS, ADC_MAX,
+                                          differential=True)
+                else:
+                    ops.xbar_noisy_linear(x, wq, wr, None, MODE, factor, rows,
+                                          ADC_BITS, ADC_MAX,
+                                          differential=True)
+            return reps
+
+        def run_eager_diff():
+            xm = ref.xbar_conv_rows(x, spec['w'][2], spec['w'][3], 1, 0) \
+                if conv else x
+            eager_diff(xm, wq_cols, fw_cols, factor, rows, step_u, inv_step_u,
+                       qu)
+            return 1
+
         variants = {'xbar': run_xbar, 'unblocked': run_unblocked,
-                    'eager': run_eager}
+                    'eager': run_eager, 'diff': run_diff,
+                    'eager_diff': run_eager_diff}
         with torch.no_grad():
             # results must agree before speeds are compared: noise off, the
             # fused op against the eager composition on the same blocks
@@ -149,9 +210,25 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
             e = eager_blocked(xm, wq_rows, fw_rows,
                               torch.zeros(1, device=dev), rows, step,
                               inv_step, qm, fp32_matmul=True)
-            del xm
             diff = (a.float() - e.float()).abs()
             moved = float((diff > 0.5 * float(step)).float().mean())
+            # the same check for the differential op
+            if conv:
+                a = ops.xbar_noisy_conv2d(x, wq, wr, None, 1, 0, None, 0.0,
+                                          rows, ADC_BITS, ADC_MAX,
+                                          differential=True)
+                a = a.permute(0, 2, 3, 1).reshape(-1, a.shape[1])
+            else:
+                a = ops.xbar_noisy_linear(x, wq, wr, None, None, 0.0, rows,
+                                          ADC_BITS, ADC_MAX,
+                                          differential=True)
+            e = eager_diff(xm, wq_cols, fw_cols, torch.zeros(1, device=dev),
+                           rows, step_u, inv_step_u, qu, fp32_matmul=True)
+            del xm
+            # the unipolar step is half the bipolar one, below the bf16
+            # spacing of the largest outputs: round the reference alike
+            diff = (a.float() - e.to(a.dtype).float()).abs()
+            moved_diff = float((diff > 0.5 * float(step_u)).float().mean())
             for fn in variants.values():    # warm-up: code objects, allocator
                 fn()
             torch.cuda.synchronize()
@@ -172,9 +249,14 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
             'eager_ms': round(sec['eager'] * 1e3, 4),
             'xbar_over_unblocked': round(sec['xbar'] / sec['unblocked'], 3),
             'eager_over_xbar': round(sec['eager'] / sec['xbar'], 2),
+            'diff_ms': round(sec['diff'] * 1e3, 4),
+            'eager_diff_ms': round(sec['eager_diff'] * 1e3, 4),
+            'diff_over_xbar': round(sec['diff'] / sec['xbar'], 3),
+            'eager_diff_over_diff': round(sec['eager_diff'] / sec['diff'], 2),
             'rounds_ms': {k: [round(t * 1e3, 4) for t in v]
                           for k, v in rr.items()},
             'noise_off_outputs_off_by_a_step_vs_eager': moved,
+            'diff_noise_off_outputs_off_by_a_step_vs_eager': moved_diff,
         }
         print(json.dumps(res), flush=True)
         results.append(res)
@@ -182,8 +264,9 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
 
 
 def resource_usage():
-    """VGPRs / LDS / scratch of every xbar_fwd_kernel instantiation, from the
-    compiler's own remarks (device-only compile for gfx950, no GPU needed)."""
+    """VGPRs / LDS / scratch of every xbar_fwd_kernel and
+    xbar_diff_fwd_kernel instantiation, from the compiler's own remarks
+    (device-only compile for gfx950, no GPU needed)."""
     from torch.utils import cpp_extension as ce
     import sysconfig
     src = os.path.join(REPO, 'csrc', 'conv_mfma.hip')
@@ -205,8 +288,9 @@ def parse_resource_usage(text):
     for line in text.splitlines():
         m = re.search(r'Function Name: (\S+)', line)
         if m:
-            cur = {'kernel': m.group(1)} if 'xbar_fwd_kernel' in m.group(1) \
-                else None
+            cur = {'kernel': m.group(1)} \
+                if ('xbar_fwd_kernel' in m.group(1)
+                    or 'xbar_diff_fwd_kernel' in m.group(1)) else None
             if cur is not None:
                 rows.append(cur)
             continue
@@ -220,8 +304,17 @@ def parse_resource_usage(text):
     for r in rows:
         print(json.dumps(r))
     # the dynamic LDS tiles are sized at launch: (64 + 3*64) rows of 80 B
-    # (16-bit) or 144 B (fp32), on top of the static bytes reported above
+    # (16-bit) or 144 B (fp32), (64 + 5*64) rows on differential columns, on
+    # top of the static bytes reported above
+    diff = [r for r in rows if 'xbar_diff_fwd_kernel' in r['kernel']]
+    summarise('xbar_fwd_kernel', [r for r in rows if r not in diff], 256)
+    summarise('xbar_diff_fwd_kernel', diff, 384)
+    return rows
+
+
+def summarise(label, rows, lds_rows):
     print(json.dumps({
+        'summary': label,
         'kernels': len(rows),
         'max_VGPRs': max(r['VGPRs'] for r in rows),
         'max_AGPRs': max(r['AGPRs'] for r in rows),
@@ -231,8 +324,8 @@ def parse_resource_usage(text):
         'min_occupancy_waves_per_simd':
             min(r['Occupancy [waves/SIMD]'] for r in rows),
         'max_static_LDS_bytes': max(r['LDS Size [bytes/block]'] for r in rows),
-        'dynamic_LDS_bytes': {'bf16/fp16': 256 * 80, 'fp32': 256 * 144}}))
-    return rows
+        'dynamic_LDS_bytes': {'bf16/fp16': lds_rows * 80,
+                              'fp32': lds_rows * 144}}))
 
 
 def main():
@@ -257,6 +350,8 @@ def main():
                              args.rounds, args.reps):
             if not r['xbar_ms'] < r['eager_ms']:
                 slower.append((name, r['xbar_rows']))
+            if not r['diff_ms'] < r['eager_diff_ms']:
+                slower.append((name, r['xbar_rows'], 'differential'))
     if slower:
         raise SystemExit('fused op not faster than the eager composition at '
                          '%s' % slower)
