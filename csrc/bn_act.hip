@@ -640,6 +640,8 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor g, torch::Tensor x,
   int eblocks = (int)std::min<int64_t>((n + kBlock - 1) / kBlock, 8192);
   NN_DISPATCH(x.scalar_type(), "bn_act_bwd", [&] {
     using T = typename DevT<scalar_t>::type;
+    // mask threshold as the forward stored it (see common.h)
+    const float thr = stored_act_max<scalar_t>(act_max);
     if (vec16 && sizeof(T) == 2)
       hipLaunchKernelGGL((bn_act_bwd_reduce_vec_kernel<T>),
                          dim3(gx_blocks, gy), dim3(kBlock), 0, stream,
@@ -648,7 +650,7 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor g, torch::Tensor x,
                          invstd.data_ptr<float>(),
                          partial_g.data_ptr<float>(),
                          partial_gx.data_ptr<float>(),
-                         rows, C, relu ? 1 : 0, (float)act_max);
+                         rows, C, relu ? 1 : 0, thr);
     else
       hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<T>), dim3(gx_blocks, gy),
                          dim3(kBlock), 0, stream, (const T*)g.data_ptr(),
@@ -656,7 +658,7 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor g, torch::Tensor x,
                          mean.data_ptr<float>(), invstd.data_ptr<float>(),
                          partial_g.data_ptr<float>(),
                          partial_gx.data_ptr<float>(),
-                         rows, C, relu ? 1 : 0, (float)act_max);
+                         rows, C, relu ? 1 : 0, thr);
     hipLaunchKernelGGL(bn_partials_reduce_kernel,
                        dim3((C + 31) / 32), dim3(256), 0,
                        stream, partial_g.data_ptr<float>(),
@@ -673,7 +675,7 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor g, torch::Tensor x,
                            invstd.data_ptr<float>(), gamma.data_ptr<float>(),
                            sum_g.data_ptr<float>(), sum_gx.data_ptr<float>(),
                            (T*)gx.data_ptr(), n / 8, C / 8,
-                           1.0f / (float)rows, relu ? 1 : 0, (float)act_max);
+                           1.0f / (float)rows, relu ? 1 : 0, thr);
       else
         hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, true>), dim3(eblocks),
                            dim3(kBlock), 0, stream, (const T*)g.data_ptr(),
@@ -681,7 +683,7 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor g, torch::Tensor x,
                            mean.data_ptr<float>(), invstd.data_ptr<float>(),
                            gamma.data_ptr<float>(), sum_g.data_ptr<float>(),
                            sum_gx.data_ptr<float>(), (T*)gx.data_ptr(), n, C,
-                           1.0f / (float)rows, relu ? 1 : 0, (float)act_max);
+                           1.0f / (float)rows, relu ? 1 : 0, thr);
     } else {
       if (vec)
         hipLaunchKernelGGL((bn_act_bwd_apply_vec_kernel<T, false>),
@@ -691,7 +693,7 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor g, torch::Tensor x,
                            invstd.data_ptr<float>(), gamma.data_ptr<float>(),
                            sum_g.data_ptr<float>(), sum_gx.data_ptr<float>(),
                            (T*)gx.data_ptr(), n / 8, C / 8,
-                           1.0f / (float)rows, relu ? 1 : 0, (float)act_max);
+                           1.0f / (float)rows, relu ? 1 : 0, thr);
       else
         hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, false>), dim3(eblocks),
                            dim3(kBlock), 0, stream, (const T*)g.data_ptr(),
@@ -699,7 +701,7 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor g, torch::Tensor x,
                            mean.data_ptr<float>(), invstd.data_ptr<float>(),
                            gamma.data_ptr<float>(), sum_g.data_ptr<float>(),
                            sum_gx.data_ptr<float>(), (T*)gx.data_ptr(), n, C,
-                           1.0f / (float)rows, relu ? 1 : 0, (float)act_max);
+                           1.0f / (float)rows, relu ? 1 : 0, thr);
     }
   });
   HIP_CHECK_LAST();
@@ -708,11 +710,41 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor g, torch::Tensor x,
 }
 
 
+// The split entry points index g, x and y with raw pointers exactly like
+// bn_act_bwd: same shape, dtype and (NHWC or row-major) layout, and f32
+// per-channel vectors of C elements.
+static void check_bn_bwd_inputs(const char* fn, const torch::Tensor& g,
+                                const torch::Tensor& x, const torch::Tensor& y,
+                                std::initializer_list<torch::Tensor> per_c) {
+  TORCH_CHECK(x.dim() == 4 || x.dim() == 2, fn, ": expected a 4-D or 2-D x");
+  TORCH_CHECK(x.is_cuda() && g.is_cuda() && y.is_cuda(), fn,
+              ": g, x, y must be GPU tensors");
+  TORCH_CHECK(g.sizes() == x.sizes() && y.sizes() == x.sizes(), fn,
+              ": g, x, y must have the same shape");
+  TORCH_CHECK(g.scalar_type() == x.scalar_type() &&
+                  y.scalar_type() == x.scalar_type(),
+              fn, ": g, x, y must have the same dtype");
+  if (x.dim() == 4) {
+    TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                    g.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                    y.is_contiguous(at::MemoryFormat::ChannelsLast),
+                fn, ": expected channels_last g, x, y");
+  } else {
+    TORCH_CHECK(x.is_contiguous() && g.is_contiguous() && y.is_contiguous(),
+                fn, ": expected contiguous g, x, y");
+  }
+  for (const auto& t : per_c)
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                    t.is_contiguous() && t.numel() == x.size(1),
+                fn, ": per-channel tensors must be contiguous f32 [C] on the GPU");
+}
+
 // Split backward for SyncBN: reduce -> (RCCL all-reduce in Python) -> apply.
 std::vector<torch::Tensor> bn_act_bwd_reduce(torch::Tensor g, torch::Tensor x,
                                              torch::Tensor y, torch::Tensor mean,
                                              torch::Tensor invstd, bool relu,
                                              double act_max) {
+  check_bn_bwd_inputs("bn_act_bwd_reduce", g, x, y, {mean, invstd});
   int C;
   int64_t rows;
   if (x.dim() == 4) {
@@ -737,6 +769,8 @@ std::vector<torch::Tensor> bn_act_bwd_reduce(torch::Tensor g, torch::Tensor x,
   auto stream = c10::hip::getCurrentHIPStream();
   NN_DISPATCH(x.scalar_type(), "bn_act_bwd_reduce", [&] {
     using T = typename DevT<scalar_t>::type;
+    // mask threshold as the forward stored it (see common.h)
+    const float thr = stored_act_max<scalar_t>(act_max);
     if (vec16 && sizeof(T) == 2)
       hipLaunchKernelGGL((bn_act_bwd_reduce_vec_kernel<T>),
                          dim3(gx_blocks, gy), dim3(kBlock), 0, stream,
@@ -745,7 +779,7 @@ std::vector<torch::Tensor> bn_act_bwd_reduce(torch::Tensor g, torch::Tensor x,
                          invstd.data_ptr<float>(),
                          partial_g.data_ptr<float>(),
                          partial_gx.data_ptr<float>(), rows, C, relu ? 1 : 0,
-                         (float)act_max);
+                         thr);
     else
       hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<T>), dim3(gx_blocks, gy),
                          dim3(kBlock), 0, stream,
@@ -753,7 +787,7 @@ std::vector<torch::Tensor> bn_act_bwd_reduce(torch::Tensor g, torch::Tensor x,
                          (const T*)y.data_ptr(), mean.data_ptr<float>(),
                          invstd.data_ptr<float>(), partial_g.data_ptr<float>(),
                          partial_gx.data_ptr<float>(), rows, C, relu ? 1 : 0,
-                         (float)act_max);
+                         thr);
   });
   hipLaunchKernelGGL(bn_partials_reduce_kernel,
                      dim3((C + 31) / 32), dim3(256), 0, stream,
@@ -769,12 +803,17 @@ torch::Tensor bn_act_bwd_apply(torch::Tensor g, torch::Tensor x,
                                torch::Tensor sum_g, torch::Tensor sum_gx,
                                double count, bool training, bool relu,
                                double act_max) {
+  check_bn_bwd_inputs("bn_act_bwd_apply", g, x, y,
+                      {mean, invstd, gamma, sum_g, sum_gx});
+  TORCH_CHECK(count >= 1.0, "bn_act_bwd_apply: count must be >= 1");
   int C = (int)x.size(1);
   auto gx = torch::empty_like(g);
   int64_t n = x.numel();
   int eblocks = (int)std::min<int64_t>((n + kBlock - 1) / kBlock, 8192);
   NN_DISPATCH(x.scalar_type(), "bn_act_bwd_apply", [&] {
     using T = typename DevT<scalar_t>::type;
+    // mask threshold as the forward stored it (see common.h)
+    const float thr = stored_act_max<scalar_t>(act_max);
     auto stream = c10::hip::getCurrentHIPStream();
     bool vec = sizeof(T) == 2 && (C & 7) == 0;
     int vblocks = (int)std::min<int64_t>((n / 8 + kBlock - 1) / kBlock, 8192);
@@ -787,7 +826,7 @@ torch::Tensor bn_act_bwd_apply(torch::Tensor g, torch::Tensor x,
                            invstd.data_ptr<float>(), gamma.data_ptr<float>(),
                            sum_g.data_ptr<float>(), sum_gx.data_ptr<float>(),
                            (T*)gx.data_ptr(), n / 8, C / 8,
-                           1.0f / (float)count, relu ? 1 : 0, (float)act_max);
+                           1.0f / (float)count, relu ? 1 : 0, thr);
       else
         hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, true>), dim3(eblocks),
                            dim3(kBlock), 0, stream, (const T*)g.data_ptr(),
@@ -795,7 +834,7 @@ torch::Tensor bn_act_bwd_apply(torch::Tensor g, torch::Tensor x,
                            mean.data_ptr<float>(), invstd.data_ptr<float>(),
                            gamma.data_ptr<float>(), sum_g.data_ptr<float>(),
                            sum_gx.data_ptr<float>(), (T*)gx.data_ptr(), n, C,
-                           1.0f / (float)count, relu ? 1 : 0, (float)act_max);
+                           1.0f / (float)count, relu ? 1 : 0, thr);
     } else {
       if (vec)
         hipLaunchKernelGGL((bn_act_bwd_apply_vec_kernel<T, false>),
@@ -805,7 +844,7 @@ torch::Tensor bn_act_bwd_apply(torch::Tensor g, torch::Tensor x,
                            invstd.data_ptr<float>(), gamma.data_ptr<float>(),
                            sum_g.data_ptr<float>(), sum_gx.data_ptr<float>(),
                            (T*)gx.data_ptr(), n / 8, C / 8,
-                           1.0f / (float)count, relu ? 1 : 0, (float)act_max);
+                           1.0f / (float)count, relu ? 1 : 0, thr);
       else
         hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, false>), dim3(eblocks),
                            dim3(kBlock), 0, stream, (const T*)g.data_ptr(),
@@ -813,7 +852,7 @@ torch::Tensor bn_act_bwd_apply(torch::Tensor g, torch::Tensor x,
                            mean.data_ptr<float>(), invstd.data_ptr<float>(),
                            gamma.data_ptr<float>(), sum_g.data_ptr<float>(),
                            sum_gx.data_ptr<float>(), (T*)gx.data_ptr(), n, C,
-                           1.0f / (float)count, relu ? 1 : 0, (float)act_max);
+                           1.0f / (float)count, relu ? 1 : 0, thr);
     }
   });
   HIP_CHECK_LAST();

@@ -33,6 +33,20 @@ template <> DEV_INLINE _Float16 from_f32<_Float16>(float v) {
   return (_Float16)v;
 }
 
+// The ReLU/clip backward kernels re-derive the activation mask from the
+// stored OUTPUT y. A saturated element is stored as T(act_max), and that
+// rounding can go DOWN (0.7 -> 0.69921875 in bf16, 4.7 -> 4.6992 in fp16),
+// so `float(y) >= act_max` against the f32 threshold would never hold and
+// the clip would pass gradient through every saturated element. Backward
+// compares against the threshold rounded the way the forward rounded it.
+// scalar_t is the host-side ATen type (float, at::BFloat16, at::Half), all
+// round-to-nearest-even like from_f32<T>.
+template <typename scalar_t>
+inline float stored_act_max(double act_max) {
+  return static_cast<float>(
+      static_cast<scalar_t>(static_cast<float>(act_max)));
+}
+
 // ---------------------------------------------------------------------------
 // Philox4x32-10 counter-based RNG
 // ---------------------------------------------------------------------------

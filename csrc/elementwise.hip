@@ -346,16 +346,19 @@ torch::Tensor relu_clip_bwd(torch::Tensor g, torch::Tensor y, bool relu,
   auto gc = g.contiguous(y.suggest_memory_format());
   auto out = torch::empty_like(gc);
   int64_t n = gc.numel();
+  TORCH_CHECK(gc.scalar_type() == yc.scalar_type() &&
+                  gc.sizes() == yc.sizes(),
+              "relu_clip_bwd: g and y must have the same dtype and shape");
   NN_DISPATCH(gc.scalar_type(), "relu_clip_bwd", [&] {
     using T = typename DevT<scalar_t>::type;
-    float lo = relu ? 0.0f : -INFINITY;
-    float hi = act_max > 0 ? (float)act_max : INFINITY;
-    // reuse ste_mask semantics: zero where y <= lo or y >= hi
+    // zero where y <= 0 (relu) or y >= the threshold AS STORED by the
+    // forward (stored_act_max, common.h)
+    const float thr = stored_act_max<scalar_t>(act_max);
     hipLaunchKernelGGL((relu_clip_bwd_kernel<T>), dim3(grid_1d(n)),
                        dim3(kBlock), 0, c10::hip::getCurrentHIPStream(),
                        (const T*)gc.data_ptr(), (const T*)yc.data_ptr(),
                        (T*)out.data_ptr(), n, relu ? 1 : 0,
-                       act_max > 0 ? (float)act_max : 0.0f);
+                       act_max > 0 ? thr : 0.0f);
   });
   HIP_CHECK_LAST();
   return out;

@@ -105,7 +105,9 @@ torch::Tensor softmax_xent_bwd(torch::Tensor softmax, torch::Tensor target,
   auto tgt = target.contiguous();
   int64_t n = nrows * ncols;
   int blocks = (int)std::min<int64_t>((n + 255) / 256, 8192);
-  float scale = (float)(gscale / (double)nrows);
+  // the same two f32 factors and the same f32 product as the device-scalar
+  // form below forms in the kernel: the two routes agree bit for bit
+  float scale = (float)(1.0 / (double)nrows) * (float)gscale;
   NN_DISPATCH(softmax.scalar_type(), "softmax_xent_bwd", [&] {
     using T = typename DevT<scalar_t>::type;
     hipLaunchKernelGGL((softmax_xent_bwd_kernel<T>), dim3(blocks), dim3(256), 0,

@@ -898,6 +898,22 @@ def add_weight_noise(w, a):
 # ---------------------------------------------------------------------------
 
 
+def _act_mask(y, relu, act_max):
+    """Activation mask re-derived from the stored output y: dy/dz = 1 where
+    0 < y (< act_max if clipped). A saturated element is stored as act_max
+    ROUNDED to y's dtype (0.7 is 0.69921875 in bf16), so y is compared with
+    that stored value: against the f32 threshold a threshold that rounds
+    down would never mask. Same rule as the HIP kernels (stored_act_max in
+    csrc/common.h)."""
+    mask = torch.ones_like(y, dtype=torch.bool)
+    if relu:
+        mask &= y > 0
+    if act_max > 0:
+        thr = torch.tensor(float(act_max), dtype=torch.float32).to(y.dtype)
+        mask &= y < thr
+    return mask
+
+
 class BnAct(torch.autograd.Function):
     """BN (train: batch stats; eval: running stats) fused with ReLU and an
     optional upper clip. Backward folds the activation mask into the BN
@@ -940,7 +956,8 @@ class BnAct(torch.autograd.Function):
             if use_native(x):
                 mean, var = ext().bn_stats(_nhwc(x) if x.dim() == 4 else x.contiguous())
             else:
-                mean, var = ref.bn_stats(x)
+                # f32 statistics whatever the storage dtype, as the kernel
+                mean, var = ref.bn_stats(x.float())
             if ws > 1:
                 stats = torch.stack([mean, var + mean * mean])
                 dist.all_reduce(stats)
@@ -1004,13 +1021,7 @@ class BnAct(torch.autograd.Function):
             return (gx, g_gamma.to(weight.dtype),
                     g_beta.to(weight.dtype)) + (None,) * 8
         shape = (1, -1, 1, 1) if x.dim() == 4 else (1, -1)
-        # activation mask: dy/dz = 1 where 0 < y (< act_max if clipped)
-        mask = torch.ones_like(y)
-        if ctx.relu:
-            mask = mask * (y > 0).to(g.dtype)
-        if ctx.act_max > 0:
-            mask = mask * (y < ctx.act_max).to(g.dtype)
-        g = (g * mask).float()
+        g = (g * _act_mask(y, ctx.relu, ctx.act_max).to(g.dtype)).float()
         dims = (0, 2, 3) if x.dim() == 4 else (0,)
         xhat = (x.float() - mean.view(shape)) * invstd.view(shape)
         g_gamma = (g * xhat).sum(dims)
@@ -1089,8 +1100,14 @@ class MaxPoolNHWC(torch.autograd.Function):
             gx = ext().maxpool_bwd(_nhwc(g), code, x_shape[2], x_shape[3],
                                    k, stride, pad)
         else:
-            gx = F.max_unpool2d(g, code, k, stride, pad,
-                                output_size=x_shape[2:])
+            # windows overlap when stride < k: accumulate (max_unpool2d
+            # overwrites, keeping one window's gradient per cell)
+            n, c = x_shape[:2]
+            gx = torch.zeros(n, c, x_shape[2] * x_shape[3],
+                             dtype=torch.float32, device=g.device)
+            gx.scatter_add_(2, code.reshape(n, c, -1),
+                            g.reshape(n, c, -1).float())
+            gx = gx.view(x_shape).to(g.dtype)
         return gx, None, None, None
 
 
@@ -1113,16 +1130,17 @@ class AvgPoolNHWC(torch.autograd.Function):
             gx = ext().avgpool_bwd(_nhwc(g), x_shape[2], x_shape[3], k,
                                    stride, pad)
         else:
-            # distribute g/(k*k) over each window via conv_transpose of ones
-            w = torch.ones(x_shape[1], 1, k, k, device=g.device,
-                           dtype=g.dtype) / (k * k)
-            gx = F.conv_transpose2d(g, w, None, stride, pad,
-                                    groups=x_shape[1],
-                                    output_padding=0)
-            # pad to original size if needed
-            if gx.shape[2] != x_shape[2] or gx.shape[3] != x_shape[3]:
-                gx = F.pad(gx, (0, x_shape[3] - gx.shape[3],
-                                0, x_shape[2] - gx.shape[2]))
+            # the pool is linear: its f32 autograd gradient at any point.
+            # (A conv_transpose of ones with the pool's padding crops the
+            # far edge as well and lost the last row/column a window
+            # reaches, e.g. 8x8 k3 s2 p1; in a 16-bit dtype its rounded
+            # 1/(k*k) also biased every cell.)
+            with torch.enable_grad():
+                xz = torch.zeros(x_shape, dtype=torch.float32,
+                                 device=g.device, requires_grad=True)
+                (gx,) = torch.autograd.grad(
+                    F.avg_pool2d(xz, k, stride, pad), xz, g.float())
+            gx = gx.to(g.dtype)
         return gx, None, None, None
 
 
@@ -1228,7 +1246,8 @@ class ActFn(torch.autograd.Function):
         ctx.save_for_backward(x)
         if use_native(x):
             return ext().act_fwd(x, _ACT_IDS[act])
-        return _act_ref_fwd(x, act)
+        # f32 arithmetic and one rounding, as the kernel
+        return _act_ref_fwd(x.float(), act).to(x.dtype)
 
     @staticmethod
     def backward(ctx, g):
@@ -1238,7 +1257,7 @@ class ActFn(torch.autograd.Function):
             # .contiguous() here forced an NCHW round-trip of every
             # channels_last activation grad (5.3 ms/step on EffNet-B0)
             return ext().act_bwd(g, x, _ACT_IDS[ctx.act]), None
-        return _act_ref_bwd(g, x, ctx.act), None
+        return _act_ref_bwd(g.float(), x.float(), ctx.act).to(g.dtype), None
 
 
 def swish(x):
@@ -1286,12 +1305,7 @@ class ReluClip(torch.autograd.Function):
             # wrapper aligns g to y's memory format (no NCHW round-trip)
             return (ext().relu_clip_bwd(g, y, bool(ctx.relu),
                                         float(ctx.act_max)), None, None)
-        mask = torch.ones_like(y)
-        if ctx.relu:
-            mask = mask * (y > 0).to(g.dtype)
-        if ctx.act_max > 0:
-            mask = mask * (y < ctx.act_max).to(g.dtype)
-        return g * mask, None, None
+        return g * _act_mask(y, ctx.relu, ctx.act_max).to(g.dtype), None, None
 
 
 def relu_clip(x, act_max=0.0, relu=True):
