@@ -118,7 +118,11 @@ torch::Tensor conv_wgrad_im2col(torch::Tensor gy, torch::Tensor x,
                                 int64_t S);
 torch::Tensor conv_wgrad_patch(torch::Tensor gy, torch::Tensor x,
                                int64_t stride, int64_t pad, int64_t R,
-                               int64_t S);
+                               int64_t S,
+                               c10::optional<torch::Tensor> x_padded);
+std::string conv_wgrad_route(int64_t C, int64_t H, int64_t W, int64_t K,
+                             int64_t R, int64_t S, int64_t stride,
+                             int64_t pad, int64_t elem_size);
 
 // conv_pool_fused.hip
 bool conv_pool_eligible(int64_t C, int64_t H, int64_t W, int64_t K, int64_t R,
@@ -222,7 +226,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_dgrad", &conv_dgrad);
   m.def("conv_wgrad", &conv_wgrad);
   m.def("conv_wgrad_im2col", &conv_wgrad_im2col);
-  m.def("conv_wgrad_patch", &conv_wgrad_patch);
+  m.def("conv_wgrad_patch", &conv_wgrad_patch, py::arg("gy"), py::arg("x"),
+        py::arg("stride"), py::arg("pad"), py::arg("R"), py::arg("S"),
+        py::arg("x_padded") = py::none());
+  m.def("conv_wgrad_route", &conv_wgrad_route);
   m.def("conv_wgrad_from_col", &conv_wgrad_from_col);
   m.def("conv_pool_eligible", &conv_pool_eligible);
   m.def("conv_fused_route", &conv_fused_route);

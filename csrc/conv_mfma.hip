@@ -1229,6 +1229,265 @@ void conv_wgrad_patch_kernel(const T* __restrict__ gy,
       }
 }
 
+// --------------------------------------------------------------------------
+// Window-staged patch wgrad (16-bit types). Same GEMM, same partials and the
+// same per-element MFMA chain as conv_wgrad_patch_kernel, but both operands
+// sit in LDS row-major, as they are in memory, and the fragments (m is the
+// contraction index) are formed with the transposed LDS read
+// ds_read_b64_tr_b16: two 4-row reads per 8-element fragment.
+//   * a block owns one k-tile and up to 384 columns of ONE filter row r
+//     (8 waves as 2 k-halves x 4 column groups of 6 fragments). All taps of
+//     a filter row read the same input rows, so per 128-m round the x
+//     operand is a window of the <= nslots input rows ih = oh*stride-pad+r
+//     that the round's output rows touch, staged once at pixel pitch
+//     `pitch` with a zero halo of `pad` pixels on both sides. Rows outside
+//     the image are staged as zeros and one extra all-zero slot serves
+//     m >= M, so padding is an address choice, never a lane mask.
+//   * the im2col gather is a per-round table of pixel byte offsets (one
+//     entry per m) plus a per-lane constant column offset s*pitch + 2*c;
+//     the MFMA loop has no divisions and no selects.
+//   * gy is staged [128 m][128 k] with 256-B rows under the XOR swizzle
+//     chunk ^= ((row&3)<<2 | (row>>2)&3), which keeps the transposed reads
+//     conflict-free; the next round's global loads are issued into
+//     registers before the MFMAs of the current one.
+// --------------------------------------------------------------------------
+
+constexpr int WW_THREADS = 512;
+constexpr int WW_FN = 6;                     // column fragments per wave
+constexpr int WW_WCOLS = WW_FN * 16;         // 96 columns per wave
+constexpr int WW_COLS = 4 * WW_WCOLS;        // 384 columns per block
+constexpr int WW_GY_BYTES = 128 * 256;
+constexpr int WW_TAB_BYTES = 128 * 4;
+constexpr int WW_XCH = 4;                    // 16-B window chunks per thread
+constexpr int WW_MAX_LDS = 144 * 1024;
+
+struct WinGeom {
+  int H, W, OH, OW, S, Cp, Kp, CRSp, stride, pad;
+  int nslots;       // output rows a 128-m round can touch
+  int pitch;        // LDS bytes per pixel (Cp*2, +16 when that is 0 mod 32)
+  int slot_bytes;   // (W + 2*pad) * pitch
+  int row_chunks;   // W*Cp/8: 16-B chunks of one input row
+  int pix_chunks;   // Cp/8
+  int ncolblk;      // column blocks per filter row
+  int noh;          // N*OH
+};
+
+typedef unsigned int ww_u32x4 __attribute__((ext_vector_type(4)));
+typedef short ww_s16x4 __attribute__((ext_vector_type(4)));
+typedef short ww_s16x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(3))) ww_s16x4 ww_lds_s16x4;
+
+// 8-element MFMA fragment from two transposed 4-row reads. Every lane of
+// the wave must be active and both addresses 8-byte aligned.
+template <typename T>
+DEV_INLINE typename Mma<T>::frag ww_tr_frag(char* lo_rows, char* hi_rows) {
+  ww_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ww_lds_s16x4*)lo_rows);
+  ww_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ww_lds_s16x4*)hi_rows);
+  ww_s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(typename Mma<T>::frag, v);
+}
+
+template <typename T>
+__global__ __launch_bounds__(WW_THREADS)
+void conv_wgrad_window_kernel(const T* __restrict__ gy,
+                              const T* __restrict__ x,
+                              float* __restrict__ dw /* [z][Kp, CRSp] f32 */,
+                              int M, WinGeom g, int mchunks_per_block) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* g_lds = smem;                                   // [128 m][128 k]
+  int* tab = (int*)(smem + WW_GY_BYTES);                // [128 m] pixel offset
+  char* x_lds = smem + WW_GY_BYTES + WW_TAB_BYTES;      // [nslots + 1] rows
+
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int wid = __builtin_amdgcn_readfirstlane(tid) / WAVE;  // wave-uniform
+  const int wm = wid >> 2, wn = wid & 3;
+  const int r = blockIdx.x / g.ncolblk;                 // filter row
+  const int cbase = (blockIdx.x - r * g.ncolblk) * WW_COLS;
+  const int rowcols = g.S * g.Cp;                       // columns of a filter row
+  const int k0 = blockIdx.y * 128;
+  const ww_u32x4 zero4 = {0u, 0u, 0u, 0u};
+
+  // halo pixels and the zero slot are written here and never again
+  const int xbytes = (g.nslots + 1) * g.slot_bytes;
+  for (int o = tid * 16; o < xbytes; o += WW_THREADS * 16)
+    *(ww_u32x4*)(x_lds + o) = zero4;
+
+  // this thread's window chunks: the same (slot, pixel, chunk) every round
+  const int nchunks = g.nslots * g.row_chunks;
+  int xslot[WW_XCH], xdst[WW_XCH], xsrc[WW_XCH];
+#pragma unroll
+  for (int i = 0; i < WW_XCH; ++i) {
+    int idx = tid + i * WW_THREADS;
+    int j = idx / g.row_chunks;
+    int rc = idx - j * g.row_chunks;
+    int px = rc / g.pix_chunks;
+    int cc = rc - px * g.pix_chunks;
+    xslot[i] = idx < nchunks ? j : -1;
+    xdst[i] = j * g.slot_bytes + (g.pad + px) * g.pitch + cc * 16;
+    xsrc[i] = rc * 8;
+  }
+
+  // transposed-read addresses. Lane 4q+p of a 16-lane group addresses row q,
+  // elements 4p..4p+3 of the block; group gq holds m = 32ks + 8gq + 0..7.
+  const int gq = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+  int aoff[4][2];
+#pragma unroll
+  for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      int row = 8 * gq + 4 * h + q;                     // + 32*ks
+      int sw = (q << 2) | ((2 * gq + h) & 3);           // same for every ks
+      int ch = wm * 8 + fm * 2 + (p >> 1);
+      aoff[fm][h] = 256 * row + 16 * (ch ^ sw) + 8 * (p & 1);
+    }
+  const int cols_blk = min(WW_COLS, rowcols - cbase);
+  int coff[WW_FN];
+#pragma unroll
+  for (int fn = 0; fn < WW_FN; ++fn) {
+    int col = cbase + wn * WW_WCOLS + fn * 16 + 4 * p;
+    if (col >= rowcols) col = 0;                        // discarded columns
+    int s = col / g.Cp;
+    coff[fn] = s * g.pitch + (col - s * g.Cp) * 2;
+  }
+  const bool wave_on = (k0 + wm * 64 < g.Kp) && (wn * WW_WCOLS < cols_blk);
+
+  f32x4 acc[4][WW_FN] = {};
+
+  const int m_start = blockIdx.z * mchunks_per_block * WG_BK;
+  const int m_end = min(m_start + mchunks_per_block * WG_BK, M);
+
+  ww_u32x4 greg[4], xreg[WW_XCH];
+  int tabreg = 0;
+  auto prefetch = [&](int m0) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int idx = tid + i * WW_THREADS;
+      int m = m0 + (idx >> 4);
+      int k = k0 + (idx & 15) * 8;
+      greg[i] = zero4;
+      if (m < M && k + 8 <= g.Kp)
+        greg[i] = *(const ww_u32x4*)(gy + (int64_t)m * g.Kp + k);
+    }
+    const int first = m0 / g.OW;                        // first output row
+#pragma unroll
+    for (int i = 0; i < WW_XCH; ++i) {
+      int orow = first + xslot[i];
+      int n = orow / g.OH;
+      int ih = (orow - n * g.OH) * g.stride - g.pad + r;
+      bool ok = xslot[i] >= 0 && orow < g.noh && ih >= 0 && ih < g.H;
+      xreg[i] = zero4;
+      if (ok)
+        xreg[i] = *(const ww_u32x4*)(x + ((int64_t)(n * g.H + ih) * g.W) * g.Cp +
+                                     xsrc[i]);
+    }
+    if (tid < 128) {
+      int m = m0 + tid;
+      int orow = m / g.OW;
+      tabreg = m < M ? (orow - first) * g.slot_bytes +
+                           (m - orow * g.OW) * g.stride * g.pitch
+                     : g.nslots * g.slot_bytes;         // the zero slot
+    }
+  };
+
+  if (m_start < m_end) prefetch(m_start);
+  __syncthreads();                                      // window zeroed
+
+  for (int m0 = m_start; m0 < m_end; m0 += WG_BK) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int idx = tid + i * WW_THREADS;
+      int mi = idx >> 4, ch = idx & 15;
+      *(ww_u32x4*)(g_lds + 256 * mi +
+                16 * (ch ^ (((mi & 3) << 2) | ((mi >> 2) & 3)))) = greg[i];
+    }
+#pragma unroll
+    for (int i = 0; i < WW_XCH; ++i)
+      if (xslot[i] >= 0) *(ww_u32x4*)(x_lds + xdst[i]) = xreg[i];
+    if (tid < 128) tab[tid] = tabreg;
+    __syncthreads();
+    if (m0 + WG_BK < m_end) prefetch(m0 + WG_BK);
+    if (wave_on) {
+      int po[4][2];
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) po[ks][h] = tab[32 * ks + 8 * gq + 4 * h + q];
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        typename Mma<T>::frag a[4];
+#pragma unroll
+        for (int fm = 0; fm < 4; ++fm)
+          a[fm] = ww_tr_frag<T>(g_lds + aoff[fm][0] + ks * 8192,
+                                g_lds + aoff[fm][1] + ks * 8192);
+#pragma unroll
+        for (int fn = 0; fn < WW_FN; ++fn) {
+          auto b = ww_tr_frag<T>(x_lds + po[ks][0] + coff[fn],
+                                 x_lds + po[ks][1] + coff[fn]);
+#pragma unroll
+          for (int fm = 0; fm < 4; ++fm) Mma<T>::mma(a[fm], b, acc[fm][fn]);
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  if (!wave_on) return;
+  float* slab = dw + (int64_t)blockIdx.z * g.Kp * g.CRSp +
+                (int64_t)r * rowcols;
+#pragma unroll
+  for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+    for (int fn = 0; fn < WW_FN; ++fn)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        int k = k0 + wm * 64 + fm * 16 + 4 * gq + reg;
+        int c = cbase + wn * WW_WCOLS + fn * 16 + (lane & 15);
+        if (k < g.Kp && c < rowcols)
+          slab[(int64_t)k * g.CRSp + c] = acc[fm][fn][reg];
+      }
+}
+
+// Shapes the window kernel takes: the window of one round (plus the zero
+// slot) and the gy tile fit the LDS budget, and no thread stages more than
+// WW_XCH chunks of it. N only enters through `noh` and the int32 m.
+bool ww_plan(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R,
+             int64_t S, int64_t stride, int64_t pad, int64_t elem_size,
+             WinGeom* out) {
+  if (elem_size != 2 || stride < 1 || pad < 0) return false;
+  if (H + 2 * pad < R || W + 2 * pad < S) return false;
+  int64_t OH = (H + 2 * pad - R) / stride + 1;
+  int64_t OW = (W + 2 * pad - S) / stride + 1;
+  int64_t Cp = (C + 7) & ~(int64_t)7, Kp = (K + 7) & ~(int64_t)7;
+  int64_t nslots = (OW + 126) / OW + 1;
+  int64_t pitch = Cp * 2 + ((Cp * 2) % 32 == 0 ? 16 : 0);
+  int64_t slot_bytes = (W + 2 * pad) * pitch;
+  int64_t row_chunks = W * Cp / 8;
+  if (nslots * row_chunks > (int64_t)WW_XCH * WW_THREADS) return false;
+  if (WW_GY_BYTES + WW_TAB_BYTES + (nslots + 1) * slot_bytes > WW_MAX_LDS)
+    return false;
+  if (N * OH * OW > (int64_t)INT32_MAX - 2 * WG_BK ||
+      R * S * Cp * Kp > (int64_t)INT32_MAX)
+    return false;
+  if (out) {
+    WinGeom g;
+    g.H = (int)H; g.W = (int)W; g.OH = (int)OH; g.OW = (int)OW; g.S = (int)S;
+    g.Cp = (int)Cp; g.Kp = (int)Kp; g.CRSp = (int)(R * S * Cp);
+    g.stride = (int)stride; g.pad = (int)pad; g.nslots = (int)nslots;
+    g.pitch = (int)pitch; g.slot_bytes = (int)slot_bytes;
+    g.row_chunks = (int)row_chunks; g.pix_chunks = (int)(Cp / 8);
+    g.ncolblk = (int)((S * Cp + WW_COLS - 1) / WW_COLS);
+    g.noh = (int)(N * OH);
+    *out = g;
+  }
+  return true;
+}
+
+bool ww_forced_legacy() {
+  const char* e = getenv("NOISYNET_WGRAD_PATCH");
+  return e != nullptr && std::string(e) == "legacy";
+}
+
 template <typename scalar_t> struct DevT { using type = scalar_t; };
 template <> struct DevT<at::BFloat16> { using type = __hip_bfloat16; };
 template <> struct DevT<at::Half> { using type = _Float16; };
@@ -2486,6 +2745,18 @@ void launch_patch_tile(const PatchTileChoice& tile, const ConvGeom& g,
   }
 }
 
+torch::Tensor pad_cols8(const torch::Tensor& in, int64_t K8);
+
+// NOISYNET_CONV_PAD_SHARE=0 keeps the noisy patch forward on the unpadded
+// input (and its backward padding again); read per call.
+bool conv_pad_share_enabled() {
+  const char* e = getenv("NOISYNET_CONV_PAD_SHARE");
+  return e == nullptr || std::string(e) != "0";
+}
+
+// Returns {out, telemetry, x_pad}: x_pad is the [N*H*W, C_pad] channel-padded
+// copy of a 16-bit input with C % 8 != 0 that the noisy forward ran on (empty
+// otherwise); conv_wgrad_patch takes it in place of padding again.
 std::vector<torch::Tensor> conv_fwd_fused_patch_impl(
     torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
     int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
@@ -2521,6 +2792,20 @@ std::vector<torch::Tensor> conv_fwd_fused_patch_impl(
   // round32): staging loads become unconditional 16-B vectors
   const PatchTileChoice tile = patch_tile(g, (int)x.element_size(),
                                           (int)sigma_mode, telem, want_y);
+  // noisy forward of a 16-bit input with C % 8 != 0: pad the channels once
+  // and stage from the copy with 16-byte vectors (the scalar path pays two
+  // divisions per element, once per k-tile). The weight image is laid out
+  // for C_pad already, so the LDS patch and the output are bit-identical;
+  // the copy goes back to the caller for the weight gradient.
+  torch::Tensor x_pad = torch::empty({0}, x.options());
+  if (want_y && sigma_mode > 0 && x.element_size() == 2 && (g.C & 7) != 0 &&
+      conv_pad_share_enabled()) {
+    x_pad = pad_cols8(x.permute({0, 2, 3, 1})
+                          .reshape({(int64_t)g.N * g.H * g.W, (int64_t)g.C})
+                          .contiguous(), p.C_pad);
+    x = x_pad;
+    g.C = p.C_pad;
+  }
   // weight rows follow the N extent of the chosen tile
   int k_pad = tile.kind == PatchTile::Generic ? (g.K + BN - 1) / BN * BN
                                               : tile.nrows;
@@ -2580,7 +2865,7 @@ std::vector<torch::Tensor> conv_fwd_fused_patch_impl(
     }
   });
   HIP_CHECK_LAST();
-  return {out, tele};
+  return {out, tele, x_pad};
 }
 
 }  // namespace
@@ -2637,9 +2922,11 @@ std::vector<torch::Tensor> conv_fwd_fused_col_impl(
 
 }  // namespace
 
-// Returns {out, telemetry, col}: col is the flat im2col matrix when the
-// small-C route materialized one (callers pass it back to
-// conv_wgrad_from_col so backward skips the materialization), else empty.
+// Returns {out, telemetry, shared}: the flat im2col matrix when the small-C
+// route materialized one (callers pass it back to conv_wgrad_from_col so
+// backward skips the materialization), the [N*H*W, C_pad] channel-padded
+// input when the noisy patch route made one (for conv_wgrad_patch), else
+// empty.
 std::vector<torch::Tensor> conv_fwd_fused(torch::Tensor x, torch::Tensor wq,
                                           torch::Tensor wraw, torch::Tensor bias,
                                           int64_t stride, int64_t pad,
@@ -2655,7 +2942,7 @@ std::vector<torch::Tensor> conv_fwd_fused(torch::Tensor x, torch::Tensor wq,
       auto r = conv_fwd_fused_patch_impl(x, wq, wraw, bias, stride, pad,
                                          sigma_mode, factor, seed, telem,
                                          true);
-      return {r[0], r[1], empty};
+      return r;
     }
     case ConvRoute::ColSmallK:
     case ConvRoute::ColGemm:
@@ -2680,9 +2967,12 @@ std::vector<torch::Tensor> sigma_noise_conv(torch::Tensor x, torch::Tensor wraw,
                      (int)x.size(1), (int)wraw.size(0), (int)wraw.size(2),
                      (int)wraw.size(3), (int)stride, (int)pad);
   switch (conv_route(g, (int)x.element_size())) {
-    case ConvRoute::Patch:
-      return conv_fwd_fused_patch_impl(x, wraw, wraw, empty_bias, stride, pad,
-                                       sigma_mode, factor, seed, telem, false);
+    case ConvRoute::Patch: {
+      auto r = conv_fwd_fused_patch_impl(x, wraw, wraw, empty_bias, stride,
+                                         pad, sigma_mode, factor, seed, telem,
+                                         false);
+      return {r[0], r[1]};
+    }
     case ConvRoute::ColSmallK:
     case ConvRoute::ColGemm: {
       auto r = conv_fwd_fused_col_impl(x, wraw, wraw, empty_bias, stride, pad,
@@ -3072,11 +3362,25 @@ torch::Tensor conv_wgrad_im2col(torch::Tensor gy, torch::Tensor x,
   return conv_wgrad_from_col(gy, col, x.size(1), R, S);
 }
 
-// Patch wgrad: no materialized im2col (see conv_wgrad_patch_kernel).
-// 16-bit dtypes; any stride/pad.
+// Which kernel conv_wgrad_patch runs for a layer: "window"
+// (conv_wgrad_window_kernel) or "legacy" (conv_wgrad_patch_kernel).
+// NOISYNET_WGRAD_PATCH=legacy forces the latter; read per call. The batch
+// size is not part of the rule (beyond 2^31 output pixels the call itself
+// takes the legacy kernel).
+std::string conv_wgrad_route(int64_t C, int64_t H, int64_t W, int64_t K,
+                             int64_t R, int64_t S, int64_t stride,
+                             int64_t pad, int64_t elem_size) {
+  if (ww_forced_legacy()) return "legacy";
+  return ww_plan(1, C, H, W, K, R, S, stride, pad, elem_size, nullptr)
+             ? "window" : "legacy";
+}
+
+// Patch wgrad: no materialized im2col (see conv_wgrad_patch_kernel and
+// conv_wgrad_window_kernel). 16-bit dtypes; any stride/pad.
 torch::Tensor conv_wgrad_patch(torch::Tensor gy, torch::Tensor x,
                                int64_t stride, int64_t pad, int64_t R,
-                               int64_t S) {
+                               int64_t S,
+                               c10::optional<torch::Tensor> x_padded) {
   check_cl(gy, "conv_wgrad_patch gy");
   check_cl(x, "conv_wgrad_patch x");
   TORCH_CHECK(x.element_size() == 2, "conv_wgrad_patch: 16-bit only");
@@ -3088,7 +3392,18 @@ torch::Tensor conv_wgrad_patch(torch::Tensor gy, torch::Tensor x,
 
   // raw NHWC views (zero-copy for channels_last)
   auto x2 = x.permute({0, 2, 3, 1}).reshape({N * H * W, C});
-  torch::Tensor xp = (Cp == C) ? x2.contiguous() : pad_cols8(x2.contiguous(), Cp);
+  torch::Tensor xp;
+  if (x_padded.has_value() && x_padded->numel() > 0) {
+    // the forward's channel-padded copy of x
+    TORCH_CHECK(x_padded->dim() == 2 && x_padded->size(0) == N * H * W &&
+                    x_padded->size(1) == Cp && x_padded->is_contiguous() &&
+                    x_padded->scalar_type() == x.scalar_type() &&
+                    x_padded->device() == x.device(),
+                "conv_wgrad_patch: x_padded must be [N*H*W, round8(C)]");
+    xp = *x_padded;
+  } else {
+    xp = (Cp == C) ? x2.contiguous() : pad_cols8(x2.contiguous(), Cp);
+  }
   auto gy2 = gy.permute({0, 2, 3, 1}).reshape({M, K});
   int64_t Kp = (K + 7) & ~7;
   torch::Tensor gyp = (Kp == K) ? gy2.contiguous()
@@ -3104,6 +3419,32 @@ torch::Tensor conv_wgrad_patch(torch::Tensor gy, torch::Tensor x,
   size_t lds = (size_t)256 * WG_LSTR;
   auto parts = torch::empty({(int64_t)mslices, Kp, CRSp},
                             x.options().dtype(torch::kFloat32));
+  // the m-slices above are the legacy tile's whatever kernel runs: every
+  // output element keeps its accumulation chain, so both routes are
+  // bit-identical
+  WinGeom wg;
+  const bool window = !ww_forced_legacy() &&
+                      ww_plan(N, C, H, W, K, R, S, stride, pad,
+                              x.element_size(), &wg);
+  if (window) {
+  NN_DISPATCH(gy.scalar_type(), "conv_wgrad_window", [&] {
+    using T = typename DevT<scalar_t>::type;
+    if constexpr (sizeof(T) == 2) {
+      dim3 wgrid((unsigned)(R * wg.ncolblk), ktiles, mslices);
+      size_t wlds = (size_t)WW_GY_BYTES + WW_TAB_BYTES +
+                    (size_t)(wg.nslots + 1) * wg.slot_bytes;
+      auto* kfn = &conv_wgrad_window_kernel<T>;
+      if (wlds > 64 * 1024)
+        hipFuncSetAttribute((const void*)kfn,
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)wlds);
+      hipLaunchKernelGGL(kfn, wgrid, dim3(WW_THREADS), wlds,
+                         c10::hip::getCurrentHIPStream(),
+                         (const T*)gyp.data_ptr(), (const T*)xp.data_ptr(),
+                         parts.data_ptr<float>(), (int)M, wg, chunks);
+    }
+  });
+  } else {
   NN_DISPATCH(gy.scalar_type(), "conv_wgrad_patch", [&] {
     using T = typename DevT<scalar_t>::type;
     auto* kfn = &conv_wgrad_patch_kernel<T>;
@@ -3118,6 +3459,7 @@ torch::Tensor conv_wgrad_patch(torch::Tensor gy, torch::Tensor x,
                        (int)OH, (int)OW, (int)S, (int)Cp, (int)CRSp,
                        (int)stride, (int)pad, chunks);
   });
+  }
   HIP_CHECK_LAST();
   auto dw = parts.sum(0).narrow(0, 0, K)
                 .view({K, R, S, Cp}).narrow(3, 0, C)

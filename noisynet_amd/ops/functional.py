@@ -142,9 +142,23 @@ def _conv_dgrad_raw(g, w, stride, padding, x_shape):
     return torch.nn.grad.conv2d_input(x_shape, w, g, stride, padding)
 
 
+def _is_padded_input(shared, x):
+    """Whether the tensor a fused forward handed back for sharing is the
+    [N*H*W, round8(C)] channel-padded copy of x (conv_fwd_fused's noisy patch
+    route) and not a flat im2col matrix, whose rows are at least 2*C wide."""
+    C = x.shape[1]
+    return (shared is not None and shared.dim() == 2 and C % 8 != 0
+            and shared.shape[0] == x.shape[0] * x.shape[2] * x.shape[3]
+            and shared.shape[1] == (C + 7) // 8 * 8)
+
+
 def _conv_wgrad_raw(g, x, stride, padding, w_shape, col=None):
     if use_native(g, x):
         R, S = w_shape[2], w_shape[3]
+        if _is_padded_input(col, x):
+            # the noisy patch forward already padded x's channels to 8
+            return ext().conv_wgrad_patch(_nhwc(g), _nhwc(x), stride,
+                                          padding, R, S, col)
         if col is not None and R * S > 1 \
                 and not _os.environ.get("NOISYNET_WGRAD_NO_COL"):
             # flat im2col matrix shared from the forward pass
@@ -314,8 +328,9 @@ class _FusedNoisyConv(torch.autograd.Function):
                 telemetry_out.nsr = sum_abs_noise / max_y
                 telemetry_out.input_sparsity = (x.detach() > 0).sum() / x.numel()
         if col is not None and col.numel():
-            # the small-C route materialized the flat im2col matrix; keep
-            # it so backward's wgrad skips the re-materialization
+            # the small-C route materialized the flat im2col matrix, or the
+            # patch route a channel-padded copy of x; keep it so backward's
+            # wgrad skips the re-materialization
             ctx.save_for_backward(x, wq, col)
         else:
             ctx.save_for_backward(x, wq)
