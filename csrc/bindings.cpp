@@ -178,6 +178,19 @@ std::vector<torch::Tensor> xbar_diff_fwd_linear(
     int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
     int64_t adc_bits, torch::Tensor adc, int64_t seed, bool telem);
 
+// bit-serial inputs: in_bits-bit codes on the grid x_step, dac_bits per slice;
+// dac = fp32 [x_step, 1/x_step]
+std::vector<torch::Tensor> xbar_serial_fwd_conv(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
+    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
+    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t in_bits,
+    int64_t dac_bits, torch::Tensor dac, int64_t seed, bool telem);
+std::vector<torch::Tensor> xbar_serial_fwd_linear(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
+    int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
+    int64_t adc_bits, torch::Tensor adc, int64_t in_bits, int64_t dac_bits,
+    torch::Tensor dac, int64_t seed, bool telem);
+
 std::string conv_fused_route(int64_t C, int64_t H, int64_t W, int64_t K,
                              int64_t R, int64_t S, int64_t stride, int64_t pad,
                              int64_t elem_size);
@@ -248,4 +261,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xbar_fwd_linear", &xbar_fwd_linear);
   m.def("xbar_diff_fwd_conv", &xbar_diff_fwd_conv);
   m.def("xbar_diff_fwd_linear", &xbar_diff_fwd_linear);
+  m.def("xbar_serial_fwd_conv", &xbar_serial_fwd_conv);
+  m.def("xbar_serial_fwd_linear", &xbar_serial_fwd_linear);
 }

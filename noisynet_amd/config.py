@@ -119,6 +119,12 @@ def build_noisynet_parser():
                              'per tile, each with its own noise and a '
                              'unipolar ADC over [0, adc_max] (needs '
                              '--xbar_rows)')
+    parser.add_argument('--xbar_dac_bits', type=int, default=0, metavar='',
+                        help='bit-serial crossbar inputs: activation bits per '
+                             'cycle; every slice of every tile has its own '
+                             'noise draw and ADC conversion, --adc_max is the '
+                             'range of one slice (0 = all bits at once; needs '
+                             '--xbar_rows and --q_a, at most 4 slices)')
     return parser
 
 

@@ -350,16 +350,25 @@ def print_xbar_stats(model, args):
     NSR of the noisy layers, the share of tile partial sums the ADC clipped,
     and max |tile partial| -- the figure to pick --adc_max from. With
     --xbar_diff the clip share and the max are per column partial (W+ and W-
-    columns, unipolar ADCs)."""
+    columns, unipolar ADCs); with --xbar_dac_bits D they are per SLICE partial
+    (J = ceil(q_a / D) conversions per tile and output), so the printed max is
+    the figure for the per-slice --adc_max."""
     def mean(v):
         return float(np.mean(v)) if len(v) else float('nan')
 
     diff = getattr(args, 'xbar_diff', False)
-    adc_kind = ('differential columns, unipolar ADC, ' if diff else '')
+    dac_bits = getattr(args, 'xbar_dac_bits', 0) or 0
     clip_name = 'clipped per column' if diff else 'clipped'
+    if dac_bits > 0:
+        clip_name = 'clipped per slice'
     for k in range(args.num_layers):
         if not model.partial_absmax[k]:
             continue
+        adc_kind = ('differential columns, unipolar ADC, ' if diff else '')
+        if dac_bits > 0:
+            q_a = getattr(args, 'q_a%d' % (k + 1))
+            adc_kind = ('bit-serial inputs D={:d} J={:d}, per slice partial, '
+                        .format(dac_bits, -(-q_a // dac_bits)))
         print('\txbar layer {:d} ({:d} rows/tile, {}{:d}-bit ADC, '
               'adc_max {:g}):  power {:.3g}  NSR {:.3g}  {} {:.2%}  '
               'max|partial| {:.4g}'

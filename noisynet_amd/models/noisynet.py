@@ -36,6 +36,19 @@ power / nsr. With --xbar_rows 0 nothing changes. --xbar_diff puts W+ and W- of
 every tile on two columns, each with its own noise and a unipolar ADC over
 [0, adc_max] (ops.xbar_noisy_*(..., differential=True)); ``adc_clip`` is then
 the share of clipped COLUMN partials. It needs --xbar_rows.
+
+Bit-serial inputs (--xbar_dac_bits D > 0, with --xbar_rows): every crossbar
+layer streams its q_a<k>-bit activation code D bits per cycle, J = ceil(q_a/D)
+<= 4 slices, each slice of each tile with its own noise draw and its own ADC
+conversion, shift-added digitally (ops.xbar_noisy_*(..., in_bits, dac_bits,
+x_step)). The activation LSB x_step = max((max - min) / (2^q_a - 1), 1e-6)
+comes from the range the preceding QuantMeasure quantised with (its
+``last_range``), so every layer needs q_a<k> > 0 and a range that starts at 0.
+--adc_max is then the range of one SLICE conversion and ``adc_clip`` /
+``partial_absmax`` are per slice partial. The layer's noise factor is
+unchanged (same cell current per unit input), so the MSB slice's noise enters
+the output times 2^((J-1)D). Not combinable with --xbar_diff; bf16 carries at
+most 7-bit codes. With --xbar_dac_bits 0 nothing changes.
 """
 
 import torch
@@ -118,6 +131,10 @@ class Net(nn.Module):
         if self.xbar_diff and self.xbar_rows <= 0:
             raise ValueError('--xbar_diff needs --xbar_rows > 0: differential '
                              'columns are a mode of the tiled crossbars')
+        self.xbar_dac_bits = getattr(args, 'xbar_dac_bits', 0) or 0
+        if self.xbar_dac_bits > 0 and self.xbar_rows <= 0:
+            raise ValueError('--xbar_dac_bits needs --xbar_rows > 0: bit-serial '
+                             'inputs are a mode of the tiled crossbars')
         if self.xbar_rows > 0:
             self._check_xbar_args()
 
@@ -148,6 +165,31 @@ class Net(nn.Module):
         if q_adc > 0 and not all(m > 0 for m in adc_max):
             raise ValueError('--q_adc > 0 needs --adc_max (or every '
                              '--adc_max1..4) > 0, got %s' % adc_max)
+        D = self.xbar_dac_bits = getattr(a, 'xbar_dac_bits', 0) or 0
+        if D < 0:
+            raise ValueError('--xbar_dac_bits must be >= 0, got %d' % D)
+        if D > 0:
+            if self.xbar_diff:
+                raise ValueError('--xbar_dac_bits cannot be combined with '
+                                 '--xbar_diff: differential columns with '
+                                 'bit-serial inputs are not built')
+            for k in (1, 2, 3, 4):
+                q_a = getattr(a, 'q_a%d' % k)
+                if q_a <= 0:
+                    raise ValueError(
+                        '--xbar_dac_bits needs a quantised input on every '
+                        'layer: --q_a%d is 0' % k)
+                if q_a > 8 or (q_a == 8 and getattr(a, 'bf16', False)):
+                    raise ValueError(
+                        '--xbar_dac_bits: --q_a%d %d is too wide; activation '
+                        'codes have at most 8 bits, 7 with --bf16 (bf16 does '
+                        'not carry every 8-bit code)' % (k, q_a))
+                if -(-q_a // D) > 4:
+                    raise ValueError(
+                        '--xbar_dac_bits %d cuts --q_a%d %d into %d slices, at '
+                        'most 4 are built; the smallest --xbar_dac_bits that '
+                        'works is %d' % (D, k, q_a, -(-q_a // D),
+                                         -(-q_a // 4)))
         flags = self._introspective_flags()
         if flags:
             raise ValueError(
@@ -205,12 +247,30 @@ class Net(nn.Module):
             self.input_sparsity[layer_num].append(float(telem.input_sparsity))
         return out
 
+    def _xbar_serial_args(self, layer_num):
+        """in_bits / dac_bits / x_step of a layer under --xbar_dac_bits: the
+        code width is the layer's q_a, the LSB that of the range its
+        QuantMeasure has just quantised with."""
+        if self.xbar_dac_bits <= 0:
+            return {}
+        k = layer_num + 1
+        q_a = getattr(self.args, 'q_a%d' % k)
+        lo, hi = getattr(self, 'quantize%d' % k).last_range
+        if lo != 0:
+            raise ValueError(
+                '--xbar_dac_bits: quantize%d has the range minimum %g; '
+                'bit-serial inputs need unsigned codes (a range from 0)'
+                % (k, lo))
+        return dict(in_bits=q_a, dac_bits=self.xbar_dac_bits,
+                    x_step=max((hi - lo) / (2.0 ** q_a - 1.0), 1e-6))
+
     def _xbar_layer(self, x, layer, current, merged_dac, i, layer_num,
                     is_conv):
         """The layer on tiled crossbars: per-tile noise when its current is
         > 0 and per-tile ADC when --q_adc > 0 (ops.xbar_noisy_*). A layer with
         neither is the plain layer, which tiling does not change. With
-        --xbar_diff every tile runs on differential columns."""
+        --xbar_diff every tile runs on differential columns, with
+        --xbar_dac_bits on bit-serial inputs."""
         a = self.args
         q_adc = getattr(a, 'q_adc', 0) or 0
         if current <= 0 and q_adc == 0:
@@ -234,18 +294,19 @@ class Net(nn.Module):
                     sigma_mode = 'abs2'
                     power_denom = input_max
         telem = ops.XbarTelemetry() if want_telemetry else None
+        serial = self._xbar_serial_args(layer_num)
         if is_conv:
             out = ops.xbar_noisy_conv2d(
                 x, wq, w_raw.detach(), bias, 1, 0, sigma_mode, factor,
                 self.xbar_rows, q_adc, adc_max, current=current,
                 power_denom=power_denom, want_telemetry=want_telemetry,
-                telemetry_out=telem, differential=self.xbar_diff)
+                telemetry_out=telem, differential=self.xbar_diff, **serial)
         else:
             out = ops.xbar_noisy_linear(
                 x, wq, w_raw.detach(), bias, sigma_mode, factor,
                 self.xbar_rows, q_adc, adc_max, current=current,
                 power_denom=power_denom, want_telemetry=want_telemetry,
-                telemetry_out=telem, differential=self.xbar_diff)
+                telemetry_out=telem, differential=self.xbar_diff, **serial)
         if want_telemetry:
             if telem.power is not None:
                 self.power[layer_num].append(float(telem.power))

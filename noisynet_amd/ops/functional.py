@@ -628,7 +628,13 @@ class XbarTelemetry(NoiseTelemetry):
     With differential columns both figures are per COLUMN partial: the share
     is over the 2 * nblocks * M * K column values v+ / v- (beyond the top code
     or below zero), ``partial_absmax`` is the max |v+-|, and nsr uses the
-    digital difference of the two columns' noises."""
+    digital difference of the two columns' noises.
+
+    With bit-serial inputs (``dac_bits`` > 0, J slices) both figures are per
+    SLICE partial: the share is over the J * nblocks * M * K values v_bj and
+    ``partial_absmax`` is the max |v_bj| -- the number to size the per-slice
+    ``adc_max`` from, much smaller than the unsliced one. power is what the
+    unsliced op reports for on-grid inputs; nsr uses the shift-added noise."""
 
     __slots__ = ("adc_clip_share", "partial_absmax")
 
@@ -644,18 +650,26 @@ _XBAR_MODE = {None: 0, "abs": 1, "abs2": 2}
 
 def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
                   sigma_mode, factor, xbar_rows, adc_bits, adc_max,
-                  want_telemetry, differential=False):
+                  want_telemetry, differential=False, in_bits=0, dac_bits=0,
+                  x_step=None):
     """Shared forward of the two xbar Functions. Returns (y, tele) with tele a
     dict of 0-dim tensors (or None): sigma_abs, abs_noise, max_y, clipped,
     n_partials, partial_absmax -- sums over the whole call. ``differential``
-    runs W+ / W- columns with unipolar ADCs (two partials per block)."""
+    runs W+ / W- columns with unipolar ADCs (two partials per block);
+    ``dac_bits`` > 0 streams the input in J slices (J partials per block)."""
     x = x2_or_x
     differential = bool(differential)
     adc = ref.xbar_adc_params(adc_bits, adc_max, x.device,
                               unipolar=differential)
     n_rows = wq[0].numel()
     nblocks = -(-n_rows // int(xbar_rows))
-    if differential:
+    dac, serial, slices = None, (), 1
+    if dac_bits:
+        slices = -(-int(in_bits) // int(dac_bits))
+        dac = ref.xbar_dac_params(x_step, x.device)
+        serial = (int(in_bits), int(dac_bits), dac)
+        fwd_conv, fwd_linear = "xbar_serial_fwd_conv", "xbar_serial_fwd_linear"
+    elif differential:
         fwd_conv, fwd_linear = "xbar_diff_fwd_conv", "xbar_diff_fwd_linear"
     else:
         fwd_conv, fwd_linear = "xbar_fwd_conv", "xbar_fwd_linear"
@@ -666,7 +680,7 @@ def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
                   _factor_tensor(factor, x.device) if sigma_mode is not None
                   else torch.zeros(1, device=x.device, dtype=torch.float32),
                   int(xbar_rows), int(adc_bits),
-                  adc if adc is not None else empty_f,
+                  adc if adc is not None else empty_f) + serial + (
                   _next_seed(x.device), bool(want_telemetry))
         wr = w_raw if sigma_mode is not None else wq
         if is_conv:
@@ -681,7 +695,7 @@ def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
         if want_telemetry:
             tele = dict(sigma_abs=t[0], abs_noise=t[1], max_y=t[2],
                         clipped=t[3],
-                        n_partials=(2 if differential else 1) * nblocks
+                        n_partials=(2 if differential else slices) * nblocks
                         * y.numel(),
                         partial_absmax=t[4])
         return y, tele
@@ -699,7 +713,8 @@ def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
             else None,
             bias.detach() if bias is not None else None, sigma_mode, factor,
             int(xbar_rows), adc_bits, adc, stats=tele,
-            differential=differential)
+            differential=differential, dac=dac, in_bits=int(in_bits),
+            dac_bits=int(dac_bits))
         if is_conv:
             N, K = x.shape[0], wq.shape[0]
             oh = (x.shape[2] + 2 * padding - R) // stride + 1
@@ -730,17 +745,20 @@ class _XbarNoisyConv(torch.autograd.Function):
     noise and the ADC: exactly the gradients of the unblocked conv with wq.
     A clipped STE would need per-block saturation masks and is not built.
     ``differential`` selects xbar_diff_fwd_kernel (W+ / W- columns, unipolar
-    ADCs); the backward is the same."""
+    ADCs), ``dac_bits`` > 0 xbar_serial_fwd_kernel (bit-serial inputs); the
+    backward is the same."""
 
     @staticmethod
     def forward(ctx, x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
                 xbar_rows, adc_bits, adc_max, want_telemetry, telemetry_out,
-                current, power_denom, differential=False):
+                current, power_denom, differential=False, in_bits=0,
+                dac_bits=0, x_step=None):
         ctx.stride, ctx.padding = stride, padding
         ctx.has_bias = bias is not None
         y, tele = _xbar_forward(x, True, wq, w_raw, bias, stride, padding,
                                 sigma_mode, factor, xbar_rows, adc_bits,
-                                adc_max, want_telemetry, differential)
+                                adc_max, want_telemetry, differential,
+                                in_bits, dac_bits, x_step)
         if want_telemetry and telemetry_out is not None:
             _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
                           power_denom)
@@ -757,7 +775,7 @@ class _XbarNoisyConv(torch.autograd.Function):
             gw = ConvWgrad.apply(g, x, ctx.stride, ctx.padding, wq.shape, None)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum(dim=(0, 2, 3))
-        return (gx, gw, None, gb) + (None,) * 12
+        return (gx, gw, None, gb) + (None,) * 15
 
 
 class _XbarNoisyLinear(torch.autograd.Function):
@@ -766,11 +784,13 @@ class _XbarNoisyLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
                 adc_bits, adc_max, want_telemetry, telemetry_out, current,
-                power_denom, differential=False):
+                power_denom, differential=False, in_bits=0, dac_bits=0,
+                x_step=None):
         ctx.has_bias = bias is not None
         y, tele = _xbar_forward(x, False, wq, w_raw, bias, 1, 0, sigma_mode,
                                 factor, xbar_rows, adc_bits, adc_max,
-                                want_telemetry, differential)
+                                want_telemetry, differential, in_bits,
+                                dac_bits, x_step)
         if want_telemetry and telemetry_out is not None:
             _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
                           power_denom)
@@ -787,13 +807,14 @@ class _XbarNoisyLinear(torch.autograd.Function):
             gw = LinearWgrad.apply(g, x)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum(dim=0)
-        return (gx, gw, None, gb) + (None,) * 10
+        return (gx, gw, None, gb) + (None,) * 13
 
 
 def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
                       xbar_rows, adc_bits, adc_max, current=0.0,
                       power_denom=1.0, want_telemetry=False,
-                      telemetry_out=None, differential=False):
+                      telemetry_out=None, differential=False, in_bits=0,
+                      dac_bits=0, x_step=None):
     """Noisy conv on tiled crossbars.
 
     The contraction index is the filter's memory order (r, s, c), c fastest;
@@ -832,32 +853,65 @@ def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
     where each column carries a non-negative current. The telemetry's ADC
     figures are then per column partial (2 * nblocks per output). The backward
     is unchanged.
+
+    ``dac_bits`` = D > 0 streams the activation bit-serially: x is an
+    ``in_bits`` = B bit code on the grid ``x_step`` (the activation LSB, a
+    positive number or 1-element tensor) and reaches the rows D bits per
+    cycle, J = ceil(B / D) <= 4 slices. B is 1..8, at most 7 for bf16 (which
+    does not carry every 8-bit code). Per block b and slice j, in fp32,
+        code = clamp(rint(x * (1/x_step)), 0, 2^B - 1)
+        d_j  = (code >> j*D) & (2^D - 1)       (the top slice may be narrower)
+        p_bj = x_step * sum d_j*wq     s_bj = max(x_step * sum d_j*f(|w_raw|), 0)
+        v_bj = p_bj + eps_bj * sqrt(factor * s_bj)   own draw per (b, j)
+        q_bj = step * clamp(rint(v_bj * (1/step)), -Qm, Qm)
+    and out = sum_b sum_j 2^(jD) q_bj + bias (b ascending, j ascending inside
+    b), rounded once. The op RE-QUANTISES its input: negative values clamp to
+    code 0 and off-grid values round to the grid, so feed it the output of
+    the activation quantiser with that quantiser's step. ``factor`` is the
+    one of the unsliced layer -- the model is "same cell current per unit
+    input, one conversion per slice" -- so the noise drawn in slice j is
+    multiplied by 2^(jD) in the shift-add and the output noise variance is
+    factor * sum_b sum_j 4^(jD) s_bj, larger than the unsliced
+    factor * sum_b s_b. ``adc_max`` is the range of ONE slice conversion; the
+    partials are much smaller than unsliced ones (read ``partial_absmax``).
+    The telemetry's ADC figures are per slice partial (J * nblocks per
+    output). ``dac_bits`` = 0 is the op without slicing. Differential columns
+    with bit-serial inputs are not built. The backward is unchanged.
     """
     if isinstance(stride, (tuple, list)):
         stride = stride[0]
     if isinstance(padding, (tuple, list)):
         padding = padding[0]
+    if dac_bits:
+        ref.xbar_check_serial_args(in_bits, dac_bits, x_step, x.dtype,
+                                   sigma_mode, adc_bits, differential)
     ref.xbar_check_args(sigma_mode, xbar_rows, adc_bits, adc_max)
     return _XbarNoisyConv.apply(x, wq, w_raw, bias, stride, padding,
                                 sigma_mode, factor, xbar_rows, adc_bits,
                                 adc_max, want_telemetry, telemetry_out,
-                                current, power_denom, bool(differential))
+                                current, power_denom, bool(differential),
+                                in_bits, dac_bits, x_step)
 
 
 def xbar_noisy_linear(x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
                       adc_bits, adc_max, current=0.0, power_denom=1.0,
                       want_telemetry=False, telemetry_out=None,
-                      differential=False):
+                      differential=False, in_bits=0, dac_bits=0, x_step=None):
     """Noisy linear layer on tiled crossbars: xbar_noisy_conv2d with the input
     index as the crossbar row. Same straight-through backward (the gradients
     of F.linear(x, wq, bias)); a clipped STE is out of scope.
     ``differential=True`` selects the W+ / W- columns with unipolar ADCs
-    described there (meant for non-negative activations)."""
+    described there (meant for non-negative activations); ``dac_bits`` > 0
+    the bit-serial inputs described there (``in_bits``, ``x_step``)."""
+    if dac_bits:
+        ref.xbar_check_serial_args(in_bits, dac_bits, x_step, x.dtype,
+                                   sigma_mode, adc_bits, differential)
     ref.xbar_check_args(sigma_mode, xbar_rows, adc_bits, adc_max)
     return _XbarNoisyLinear.apply(x, wq, w_raw, bias, sigma_mode, factor,
                                   xbar_rows, adc_bits, adc_max,
                                   want_telemetry, telemetry_out, current,
-                                  power_denom, bool(differential))
+                                  power_denom, bool(differential), in_bits,
+                                  dac_bits, x_step)
 
 
 # ---------------------------------------------------------------------------

@@ -131,6 +131,50 @@ def xbar_adc_params(adc_bits, adc_max, device, unipolar=False):
     return torch.cat([step, 1.0 / step])
 
 
+def xbar_check_serial_args(in_bits, dac_bits, x_step, dtype, sigma_mode,
+                           adc_bits, differential=False):
+    """Argument rules of the bit-serial input mode (``dac_bits`` > 0); returns
+    the slice count J = ceil(in_bits / dac_bits)."""
+    if int(dac_bits) != dac_bits or dac_bits < 1:
+        raise ValueError("dac_bits must be 0 (all bits at once) or >= 1, "
+                         "got %r" % (dac_bits,))
+    if differential:
+        raise ValueError("differential columns with bit-serial inputs "
+                         "(dac_bits > 0) are not built")
+    top = 7 if dtype == torch.bfloat16 else 8
+    if int(in_bits) != in_bits or not 1 <= in_bits <= top:
+        raise ValueError(
+            "in_bits must be 1..%d for %s activations (bf16 does not carry "
+            "every 8-bit code), got %r" % (top, dtype, in_bits))
+    slices = -(-int(in_bits) // int(dac_bits))
+    if slices > 4:
+        raise ValueError(
+            "in_bits %d at dac_bits %d is %d slices, at most 4 are built; the "
+            "smallest dac_bits that works is %d"
+            % (in_bits, dac_bits, slices, -(-int(in_bits) // 4)))
+    if x_step is None:
+        raise ValueError("dac_bits > 0 needs x_step, the activation LSB")
+    if not isinstance(x_step, torch.Tensor) and not float(x_step) > 0:
+        raise ValueError("x_step must be > 0, got %r" % (x_step,))
+    if adc_bits == 0 and sigma_mode is None:
+        raise ValueError("xbar op with neither noise (sigma_mode) nor an ADC "
+                         "(adc_bits): bit-serial inputs have nothing to act on")
+    return slices
+
+
+def xbar_dac_params(x_step, device):
+    """fp32 tensor [x_step, 1/x_step], both rounded once to fp32 (the values
+    the kernel multiplies with). ``x_step`` is a number or a 1-element tensor
+    (then it must be positive; it is not read back to check)."""
+    if isinstance(x_step, torch.Tensor):
+        xs = x_step.detach().to(device=device, dtype=torch.float32).reshape(1)
+    else:
+        # a fill, not a host-to-device copy: legal under graph capture
+        xs = torch.full((1,), float(x_step), dtype=torch.float32,
+                        device=device)
+    return torch.cat([xs, 1.0 / xs])
+
+
 def xbar_conv_rows(x, R, S, stride, padding):
     """im2col matrix [N*OH*OW, R*S*C] of an NCHW input with the contraction
     index in the filter's memory order (r, s, c), c fastest -- the crossbar
@@ -150,7 +194,8 @@ def xbar_weight_rows(w):
 
 
 def xbar_vmm(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows, adc_bits,
-             adc, gen=None, stats=None, differential=False):
+             adc, gen=None, stats=None, differential=False, dac=None,
+             in_bits=0, dac_bits=0):
     """Blocked analog VMM on row matrices: xm [M, n], wqm / wrm [K, n].
 
     Block b covers rows [b*xbar_rows, min((b+1)*xbar_rows, n)). Per block
@@ -164,7 +209,15 @@ def xbar_vmm(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows, adc_bits,
     with bias), clipped (count of |rint(v_b/step)| > Qm), n_partials and
     partial_absmax (max |v_b|). Returns fp32 [M, K].
 
-    ``differential`` runs every block on two columns (see _xbar_vmm_diff)."""
+    ``differential`` runs every block on two columns (see _xbar_vmm_diff);
+    ``dac_bits`` > 0 streams the input in slices (see _xbar_vmm_serial)."""
+    if dac_bits:
+        if differential:
+            raise ValueError("differential columns with bit-serial inputs "
+                             "(dac_bits > 0) are not built")
+        return _xbar_vmm_serial(xm, wqm, wrm, bias, sigma_mode, factor,
+                                xbar_rows, adc_bits, adc, dac, in_bits,
+                                dac_bits, gen, stats)
     if differential:
         return _xbar_vmm_diff(xm, wqm, wrm, bias, sigma_mode, factor,
                               xbar_rows, adc_bits, adc, gen, stats)
@@ -297,6 +350,89 @@ def _xbar_vmm_diff(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows,
         stats.update(sigma_abs=sig_abs, abs_noise=noise_tot.abs().sum(),
                      max_y=clean.max(), clipped=clipped,
                      n_partials=2 * nblk * M * K, partial_absmax=absmax)
+    return out
+
+
+def _xbar_vmm_serial(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows,
+                     adc_bits, adc, dac, in_bits, dac_bits, gen=None,
+                     stats=None):
+    """xbar_vmm with bit-serial inputs: the activation is an ``in_bits``-bit
+    code on the grid x_step (``dac`` = [x_step, 1/x_step] of xbar_dac_params)
+    and reaches the rows ``dac_bits`` = D bits per cycle, J = ceil(B/D) slices,
+    each with its own current, noise draw and ADC conversion:
+        code = clamp(rint(x * (1/x_step)), 0, 2^B - 1)
+        d_j  = (code >> j*D) & (2^D - 1)                       j = 0..J-1
+        p_bj = x_step * (d_j @ wq_b^T)    s_bj = max(x_step * (d_j @ f_b^T), 0)
+        v_bj = p_bj + eps_bj * sqrt(factor * s_bj)
+        q_bj = step * clamp(rint(v_bj * (1/step)), -Qm, Qm)
+    and out = sum_b sum_j 2^(jD) q_bj + bias in fp32 (b ascending, j ascending
+    inside b). Negative and off-grid inputs are re-quantised to the grid.
+    ``stats``: sigma_abs = sum 2^(jD) x_step (d_j @ |w_raw|^T), abs_noise uses
+    the shift-added noises, max_y the clean shift-added sum with bias, clipped
+    counts over all (b, j) partials, n_partials = J * nblocks * M * K and
+    partial_absmax = max |v_bj| -- the figure to size a per-slice adc_max
+    from."""
+    D, B = int(dac_bits), int(in_bits)
+    J = -(-B // D)
+    x_step, inv_x_step = dac[0], dac[1]
+    code = torch.round(xm.float() * inv_x_step).clamp(0, float(2 ** B - 1))
+    code = code.to(torch.int32)
+    wqm = wqm.float()
+    n = xm.shape[1]
+    M, K = xm.shape[0], wqm.shape[0]
+    out = torch.zeros(M, K, dtype=torch.float32, device=xm.device)
+    if sigma_mode is not None:
+        aw = wrm.float().abs()
+        fw = aw * aw + aw if sigma_mode == "abs2" else aw
+        factor = torch.as_tensor(factor, dtype=torch.float32, device=xm.device)
+    if adc is not None:
+        step, inv_step = adc[0], adc[1]
+        qm = float(2 ** (int(adc_bits) - 1) - 1)
+    if stats is not None:
+        clean = torch.zeros_like(out)
+        noise_tot = torch.zeros_like(out)
+        sig_abs = out.new_zeros(())
+        clipped = 0
+        absmax = out.new_zeros(())
+        nblk = 0
+    for k0 in range(0, n, xbar_rows):
+        k1 = min(k0 + xbar_rows, n)
+        for j in range(J):
+            shift = float(2 ** (j * D))
+            dj = ((code[:, k0:k1] >> (j * D)) & (2 ** D - 1)).float()
+            p = x_step * (dj @ wqm[:, k0:k1].t())
+            v = p
+            if sigma_mode is not None:
+                s = (x_step * (dj @ fw[:, k0:k1].t())).clamp_min(0)
+                eps = torch.randn(p.shape, dtype=torch.float32,
+                                  device=p.device, generator=gen)
+                nb = eps * (factor * s).sqrt()
+                v = p + nb
+            if adc is not None:
+                t = torch.round(v * inv_step)
+                q = step * t.clamp(-qm, qm)
+            else:
+                q = v
+            out = out + shift * q
+            if stats is not None:
+                clean = clean + shift * p
+                absmax = torch.maximum(absmax, v.abs().max())
+                if sigma_mode is not None:
+                    noise_tot = noise_tot + shift * nb
+                    sig_abs = sig_abs + shift * x_step \
+                        * (dj @ aw[:, k0:k1].t()).sum()
+                if adc is not None:
+                    clipped = clipped + (t.abs() > qm).sum()
+        if stats is not None:
+            nblk += 1
+    if bias is not None:
+        out = out + bias.float()
+    if stats is not None:
+        if bias is not None:
+            clean = clean + bias.float()
+        stats.update(sigma_abs=sig_abs, abs_noise=noise_tot.abs().sum(),
+                     max_y=clean.max(), clipped=clipped,
+                     n_partials=J * nblk * M * K, partial_absmax=absmax)
     return out
 
 

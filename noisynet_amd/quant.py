@@ -81,6 +81,7 @@ class QuantMeasure(nn.Module):
         # capture). Invalidated when buffers change (finish_calibration,
         # checkpoint load).
         self._range_cache = None
+        self.last_range = None
         if pctl < 1:
             raise ValueError('pctl is {} please check'.format(pctl))
 
@@ -131,6 +132,9 @@ class QuantMeasure(nn.Module):
                     self._range_cache = (min_value, max_value)
 
             stoch = self.stochastic if self.training else 0
+            # the floats this call quantises with (bit-serial crossbar inputs
+            # derive the activation LSB from them)
+            self.last_range = (float(min_value), float(max_value))
 
         return ops.fake_quant(input, self.num_bits, min_value, max_value, stoch)
 

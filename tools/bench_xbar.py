@@ -19,6 +19,13 @@ and for xbar_rows in {64, 128, 256}:
                 and two unipolar ADCs per block, still one kernel
   (c') eager_diff  the eager composition of the differential model: four
                 bf16 matmuls per block, twice those of (c)
+  (e) serial    (a) with bit-serial inputs: in_bits 4, dac_bits 1 (J = 4
+                slices) and 2 (J = 2), J noise draws and J ADC conversions
+                per block, still one kernel
+  (c") eager_serial  the eager bit-serial composition: per block and slice two
+                bf16 matmuls, randn noise, round / clamp and the shift-add,
+                J x the matmuls of (c); the slice row matrices are built once,
+                outside the timed region
 
 Device events around windows of at least --window seconds after a warm-up,
 the variants alternating over --rounds rounds in one process; the median
@@ -27,7 +34,8 @@ CPU fallback: a time is a GPU time or it is not reported.
 
 --resource-usage needs no GPU: it compiles csrc/conv_mfma.hip for gfx950 with
 -Rpass-analysis=kernel-resource-usage and prints VGPRs, LDS and scratch of
-every xbar_fwd_kernel and xbar_diff_fwd_kernel instantiation.
+every xbar_fwd_kernel, xbar_diff_fwd_kernel and xbar_serial_fwd_kernel
+instantiation.
 """
 
 import argparse
@@ -51,6 +59,11 @@ LAYERS = {
     'linear1': dict(kind='linear', x=(2048, 3000), w=(390, 3000)),
 }
 MODE, FACTOR, ADC_BITS, ADC_MAX = 'abs2', 0.05, 6, 3.0
+# bit-serial inputs: the activations are on the 4-bit grid k/15
+IN_BITS, X_STEP, DAC_BITS = 4, 1.0 / 15.0, (1, 2)
+# a slice partial is far smaller than a full-code one: +-3 would round nearly
+# all of them to 0 and make the agreement check empty
+SERIAL_ADC_MAX = 0.25
 
 
 def eager_blocked(xm, wq, fw, factor, xbar_rows, step, inv_step, qm,
@@ -98,6 +111,38 @@ def eager_diff(xm, wq, wr, factor, xbar_rows, step, inv_step, qu, mode=MODE,
         q = qs[0] - qs[1]
         out = q if out is None else out + q
     return out
+
+
+def eager_serial(slices, wq, fw, factor, xbar_rows, step, inv_step, qm,
+                 x_step, dac_bits, fp32_matmul=False):
+    """The bit-serial model composed of stock torch ops: per block and per
+    slice a wq matmul, an f matmul, randn noise and a round / clamp, then the
+    shift-add; every partial through memory. ``slices`` are the row matrices
+    d_j, prepared once, outside the timed region."""
+    if fp32_matmul:
+        slices = [d.float() for d in slices]
+        wq, fw = wq.float(), fw.float()
+    n = wq.shape[1]
+    out = None
+    for k0 in range(0, n, xbar_rows):
+        k1 = min(k0 + xbar_rows, n)
+        for j, d in enumerate(slices):
+            xb = d[:, k0:k1]
+            p = x_step * (xb @ wq[:, k0:k1].t()).float()
+            s = (x_step * (xb @ fw[:, k0:k1].t()).float()).clamp_min(0)
+            v = p + torch.randn_like(p) * (factor * s).sqrt()
+            q = float(2 ** (j * dac_bits)) \
+                * (step * torch.round(v * inv_step).clamp(-qm, qm))
+            out = q if out is None else out + q
+    return out
+
+
+def make_slices(xm, x_step, in_bits, dac_bits):
+    inv = 1.0 / torch.tensor(x_step, dtype=torch.float32)
+    code = torch.round(xm.float() * inv.to(xm.device)) \
+        .clamp(0, 2 ** in_bits - 1).to(torch.int32)
+    return [((code >> (j * dac_bits)) & (2 ** dac_bits - 1)).to(xm.dtype)
+            for j in range(-(-in_bits // dac_bits))]
 
 
 def timed(fn, window, min_calls=3):
@@ -195,6 +240,36 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
         variants = {'xbar': run_xbar, 'unblocked': run_unblocked,
                     'eager': run_eager, 'diff': run_diff,
                     'eager_diff': run_eager_diff}
+        dac = ref.xbar_dac_params(X_STEP, dev)
+        adc_s = ref.xbar_adc_params(ADC_BITS, SERIAL_ADC_MAX, dev)
+        step_s, inv_step_s = adc_s[0], adc_s[1]
+        xm_all = ref.xbar_conv_rows(x, spec['w'][2], spec['w'][3], 1, 0) \
+            if conv else x
+        slices, moved_serial = {}, {}
+        for D in DAC_BITS:
+            slices[D] = make_slices(xm_all, X_STEP, IN_BITS, D)
+
+            def run_serial(D=D):
+                kw = dict(in_bits=IN_BITS, dac_bits=D, x_step=X_STEP)
+                for _ in range(reps):
+                    if conv:
+                        ops.xbar_noisy_conv2d(x, wq, wr, None, 1, 0, MODE,
+                                              factor, rows, ADC_BITS,
+                                              SERIAL_ADC_MAX, **kw)
+                    else:
+                        ops.xbar_noisy_linear(x, wq, wr, None, MODE, factor,
+                                              rows, ADC_BITS, SERIAL_ADC_MAX,
+                                              **kw)
+                return reps
+
+            def run_eager_serial(D=D):
+                eager_serial(slices[D], wq_rows, fw_rows, factor, rows,
+                             step_s, inv_step_s, qm, dac[0], D)
+                return 1
+
+            variants['serial_d%d' % D] = run_serial
+            variants['eager_serial_d%d' % D] = run_eager_serial
+        del xm_all
         with torch.no_grad():
             # results must agree before speeds are compared: noise off, the
             # fused op against the eager composition on the same blocks
@@ -229,6 +304,24 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
             # spacing of the largest outputs: round the reference alike
             diff = (a.float() - e.to(a.dtype).float()).abs()
             moved_diff = float((diff > 0.5 * float(step_u)).float().mean())
+            # and for the bit-serial op: outputs off by more than half a step
+            for D in DAC_BITS:
+                kw = dict(in_bits=IN_BITS, dac_bits=D, x_step=X_STEP)
+                if conv:
+                    a = ops.xbar_noisy_conv2d(x, wq, wr, None, 1, 0, None,
+                                              0.0, rows, ADC_BITS,
+                                              SERIAL_ADC_MAX, **kw)
+                    a = a.permute(0, 2, 3, 1).reshape(-1, a.shape[1])
+                else:
+                    a = ops.xbar_noisy_linear(x, wq, wr, None, None, 0.0,
+                                              rows, ADC_BITS, SERIAL_ADC_MAX,
+                                              **kw)
+                e = eager_serial(slices[D], wq_rows, fw_rows,
+                                 torch.zeros(1, device=dev), rows, step_s,
+                                 inv_step_s, qm, dac[0], D, fp32_matmul=True)
+                diff = (a.float() - e.to(a.dtype).float()).abs()
+                moved_serial[D] = float(
+                    (diff > 0.5 * float(step_s)).float().mean())
             for fn in variants.values():    # warm-up: code objects, allocator
                 fn()
             torch.cuda.synchronize()
@@ -257,7 +350,17 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
                           for k, v in rr.items()},
             'noise_off_outputs_off_by_a_step_vs_eager': moved,
             'diff_noise_off_outputs_off_by_a_step_vs_eager': moved_diff,
+            'in_bits': IN_BITS, 'serial_adc_max': SERIAL_ADC_MAX,
         }
+        for D in DAC_BITS:
+            ser, eag = sec['serial_d%d' % D], sec['eager_serial_d%d' % D]
+            res['serial_d%d_ms' % D] = round(ser * 1e3, 4)
+            res['eager_serial_d%d_ms' % D] = round(eag * 1e3, 4)
+            res['serial_d%d_over_xbar' % D] = round(ser / sec['xbar'], 3)
+            res['eager_serial_d%d_over_serial' % D] = round(eag / ser, 2)
+            res['serial_d%d_noise_off_outputs_off_by_a_step_vs_eager' % D] = \
+                moved_serial[D]
+        del slices
         print(json.dumps(res), flush=True)
         results.append(res)
     return results
@@ -290,7 +393,8 @@ def parse_resource_usage(text):
         if m:
             cur = {'kernel': m.group(1)} \
                 if ('xbar_fwd_kernel' in m.group(1)
-                    or 'xbar_diff_fwd_kernel' in m.group(1)) else None
+                    or 'xbar_diff_fwd_kernel' in m.group(1)
+                    or 'xbar_serial_fwd_kernel' in m.group(1)) else None
             if cur is not None:
                 rows.append(cur)
             continue
@@ -307,8 +411,20 @@ def parse_resource_usage(text):
     # (16-bit) or 144 B (fp32), (64 + 5*64) rows on differential columns, on
     # top of the static bytes reported above
     diff = [r for r in rows if 'xbar_diff_fwd_kernel' in r['kernel']]
-    summarise('xbar_fwd_kernel', [r for r in rows if r not in diff], 256)
+    serial = [r for r in rows if 'xbar_serial_fwd_kernel' in r['kernel']]
+    summarise('xbar_fwd_kernel',
+              [r for r in rows if r not in diff and r not in serial], 256)
     summarise('xbar_diff_fwd_kernel', diff, 384)
+    # (J*64 + 3*64) rows; the mangled name carries T (DF16b / DF16_ / f), J,
+    # SIGMA_MODE, ADC and TELEM as I<T>Li<J>ELi<mode>ELb<adc>ELb<telem>E
+    for J in (1, 2, 3, 4):
+        of_j = [r for r in serial
+                if re.search(r'kernelI\w+?Li%dELi\dELb' % J, r['kernel'])]
+        summarise('xbar_serial_fwd_kernel J=%d' % J, of_j, 64 * J + 192)
+        steady = [r for r in of_j if r['kernel'].split('ELb')[2][0] == '0'
+                  and 'kernelIf' not in r['kernel']]
+        summarise('xbar_serial_fwd_kernel J=%d, 16-bit, no telemetry' % J,
+                  steady, 64 * J + 192)
     return rows
 
 
@@ -352,6 +468,10 @@ def main():
                 slower.append((name, r['xbar_rows']))
             if not r['diff_ms'] < r['eager_diff_ms']:
                 slower.append((name, r['xbar_rows'], 'differential'))
+            for D in DAC_BITS:
+                if not r['serial_d%d_ms' % D] < r['eager_serial_d%d_ms' % D]:
+                    slower.append((name, r['xbar_rows'],
+                                   'bit-serial dac_bits %d' % D))
     if slower:
         raise SystemExit('fused op not faster than the eager composition at '
                          '%s' % slower)
