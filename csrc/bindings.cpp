@@ -55,6 +55,11 @@ torch::Tensor bn_act_bwd_apply(torch::Tensor g, torch::Tensor x,
                                torch::Tensor sum_g, torch::Tensor sum_gx,
                                double count, bool training, bool relu,
                                double act_max);
+std::vector<torch::Tensor> bn_act_quant_fwd(
+    torch::Tensor x, torch::Tensor mean, torch::Tensor invstd,
+    torch::Tensor gamma, torch::Tensor beta, bool relu, double act_max,
+    int64_t num_bits, double min_value, double max_value, double stochastic,
+    int64_t seed, int64_t C_pad);
 
 // pool.hip
 std::vector<torch::Tensor> maxpool2x2_fwd(torch::Tensor x);
@@ -104,7 +109,8 @@ std::vector<torch::Tensor> conv_fwd_fused(torch::Tensor x, torch::Tensor wq,
                                           int64_t stride, int64_t pad,
                                           int64_t sigma_mode,
                                           torch::Tensor factor,
-                                          int64_t seed, bool telem);
+                                          int64_t seed, bool telem,
+                                          c10::optional<torch::Tensor> x_padded);
 torch::Tensor conv_dgrad(torch::Tensor gy, torch::Tensor w, int64_t stride,
                          int64_t pad, int64_t H, int64_t W);
 torch::Tensor conv_wgrad(torch::Tensor gy, torch::Tensor x, int64_t stride,
@@ -219,6 +225,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_act_bwd", &bn_act_bwd);
   m.def("bn_act_bwd_reduce", &bn_act_bwd_reduce);
   m.def("bn_act_bwd_apply", &bn_act_bwd_apply);
+  m.def("bn_act_quant_fwd", &bn_act_quant_fwd);
   m.def("maxpool2x2_fwd", &maxpool2x2_fwd);
   m.def("maxpool2x2_bwd", &maxpool2x2_bwd);
   m.def("dwconv_fwd", &dwconv_fwd);
@@ -235,7 +242,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kth_percentile", &kth_percentile);
   m.def("crop_resize_mirror_normalize", &crop_resize_mirror_normalize);
   m.def("conv_fwd", &conv_fwd);
-  m.def("conv_fwd_fused", &conv_fwd_fused);
+  m.def("conv_fwd_fused", &conv_fwd_fused, py::arg("x"), py::arg("wq"),
+        py::arg("wraw"), py::arg("bias"), py::arg("stride"), py::arg("pad"),
+        py::arg("sigma_mode"), py::arg("factor"), py::arg("seed"),
+        py::arg("telem"), py::arg("x_padded") = py::none());
   m.def("conv_dgrad", &conv_dgrad);
   m.def("conv_wgrad", &conv_wgrad);
   m.def("conv_wgrad_im2col", &conv_wgrad_im2col);

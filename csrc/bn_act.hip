@@ -198,10 +198,8 @@ __global__ void bn_act_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     int c = (int)(i % C);
-    float v = (to_f32(x[i]) - mean[c]) * invstd[c] * gamma[c] + beta[c];
-    if (do_relu) v = fmaxf(v, 0.0f);
-    if (act_max > 0.0f) v = fminf(v, act_max);
-    y[i] = from_f32<T>(v);
+    y[i] = bn_act_value<T>(to_f32(x[i]), mean[c], invstd[c], gamma[c],
+                           beta[c], do_relu, act_max);
   }
 }
 
@@ -225,10 +223,8 @@ __global__ void bn_act_fwd_vec_kernel(const T* __restrict__ x,
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       int c = c0 + u;
-      float v = (to_f32(xv.v[u]) - mean[c]) * invstd[c] * gamma[c] + beta[c];
-      if (do_relu) v = fmaxf(v, 0.0f);
-      if (act_max > 0.0f) v = fminf(v, act_max);
-      o.v[u] = from_f32<T>(v);
+      o.v[u] = bn_act_value<T>(to_f32(xv.v[u]), mean[c], invstd[c], gamma[c],
+                               beta[c], do_relu, act_max);
     }
     ((V*)y)[i] = o;
   }

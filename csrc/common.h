@@ -47,6 +47,23 @@ inline float stored_act_max(double act_max) {
       static_cast<scalar_t>(static_cast<float>(act_max)));
 }
 
+// BN + ReLU + clip of one element, rounded to the storage type. The one
+// definition of the stored activation: bn_act_fwd writes it, and the fused
+// BN/quantise kernels (bn_act_quant.hip) recompute it in forward and backward
+// in place of reading it back. The roundings are spelled out (subtract,
+// multiply, then ONE fused multiply-add, contraction off for the rest), so
+// the value does not depend on which products the compiler chooses to
+// contract in a given kernel.
+template <typename T>
+DEV_INLINE T bn_act_value(float xv, float mean, float invstd, float gamma,
+                          float beta, int do_relu, float act_max) {
+#pragma clang fp contract(off)
+  float v = __fmaf_rn((xv - mean) * invstd, gamma, beta);
+  if (do_relu) v = fmaxf(v, 0.0f);
+  if (act_max > 0.0f) v = fminf(v, act_max);
+  return from_f32<T>(v);
+}
+
 // ---------------------------------------------------------------------------
 // Philox4x32-10 counter-based RNG
 // ---------------------------------------------------------------------------

@@ -2757,13 +2757,18 @@ bool conv_pad_share_enabled() {
 // Returns {out, telemetry, x_pad}: x_pad is the [N*H*W, C_pad] channel-padded
 // copy of a 16-bit input with C % 8 != 0 that the noisy forward ran on (empty
 // otherwise); conv_wgrad_patch takes it in place of padding again.
+// x_prepadded: the caller already holds that padded copy (bn_act_quant_fwd
+// writes it directly). x then gives the logical shape only and is never read;
+// the copy is run on as it is and handed back as x_pad.
 std::vector<torch::Tensor> conv_fwd_fused_patch_impl(
     torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
     int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
-    int64_t seed, bool telem, bool want_y) {
+    int64_t seed, bool telem, bool want_y,
+    const c10::optional<torch::Tensor>& x_prepadded = c10::nullopt) {
   // the noise-free S0 variant exists with the y accumulator only
   check_sigma_mode(sigma_mode, want_y, "conv_fwd_fused (patch route)");
-  check_cl(x, "conv_fwd_patch x");
+  const bool prepadded = x_prepadded.has_value() && x_prepadded->numel() > 0;
+  if (!prepadded) check_cl(x, "conv_fwd_patch x");
   auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
                      (int)x.size(1), (int)wraw.size(0), (int)wraw.size(2),
                      (int)wraw.size(3), (int)stride, (int)pad);
@@ -2798,8 +2803,23 @@ std::vector<torch::Tensor> conv_fwd_fused_patch_impl(
   // for C_pad already, so the LDS patch and the output are bit-identical;
   // the copy goes back to the caller for the weight gradient.
   torch::Tensor x_pad = torch::empty({0}, x.options());
-  if (want_y && sigma_mode > 0 && x.element_size() == 2 && (g.C & 7) != 0 &&
-      conv_pad_share_enabled()) {
+  const bool pad_route = want_y && sigma_mode > 0 && x.element_size() == 2 &&
+                         (g.C & 7) != 0 && conv_pad_share_enabled();
+  if (prepadded) {
+    TORCH_CHECK(pad_route,
+                "conv_fwd_fused: a pre-padded input is taken by the noisy "
+                "16-bit patch route with C % 8 != 0 only");
+    TORCH_CHECK(x_prepadded->dim() == 2 &&
+                    x_prepadded->size(0) == (int64_t)g.N * g.H * g.W &&
+                    x_prepadded->size(1) == p.C_pad &&
+                    x_prepadded->is_contiguous() &&
+                    x_prepadded->scalar_type() == x.scalar_type() &&
+                    x_prepadded->device() == x.device(),
+                "conv_fwd_fused: x_padded must be [N*H*W, round8(C)]");
+    x_pad = *x_prepadded;
+    x = x_pad;
+    g.C = p.C_pad;
+  } else if (pad_route) {
     x_pad = pad_cols8(x.permute({0, 2, 3, 1})
                           .reshape({(int64_t)g.N * g.H * g.W, (int64_t)g.C})
                           .contiguous(), p.C_pad);
@@ -2926,22 +2946,30 @@ std::vector<torch::Tensor> conv_fwd_fused_col_impl(
 // route materialized one (callers pass it back to conv_wgrad_from_col so
 // backward skips the materialization), the [N*H*W, C_pad] channel-padded
 // input when the noisy patch route made one (for conv_wgrad_patch), else
-// empty.
+// empty. With x_padded the caller passes that padded input in: x is then read
+// for its (logical, unpadded) shape only and the same tensor comes back as
+// the third output; only the patch route takes one.
 std::vector<torch::Tensor> conv_fwd_fused(torch::Tensor x, torch::Tensor wq,
                                           torch::Tensor wraw, torch::Tensor bias,
                                           int64_t stride, int64_t pad,
                                           int64_t sigma_mode,
                                           torch::Tensor factor,
-                                          int64_t seed, bool telem) {
+                                          int64_t seed, bool telem,
+                                          c10::optional<torch::Tensor> x_padded) {
+  TORCH_CHECK(x.dim() == 4, "conv_fwd_fused: expected a 4-D x");
   auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
                      (int)x.size(1), (int)wraw.size(0), (int)wraw.size(2),
                      (int)wraw.size(3), (int)stride, (int)pad);
   auto empty = torch::empty({0}, x.options());
-  switch (conv_route(g, (int)x.element_size())) {
+  const bool prepadded = x_padded.has_value() && x_padded->numel() > 0;
+  const ConvRoute route = conv_route(g, (int)x.element_size());
+  TORCH_CHECK(!prepadded || route == ConvRoute::Patch,
+              "conv_fwd_fused: a pre-padded input needs the patch route");
+  switch (route) {
     case ConvRoute::Patch: {
       auto r = conv_fwd_fused_patch_impl(x, wq, wraw, bias, stride, pad,
                                          sigma_mode, factor, seed, telem,
-                                         true);
+                                         true, x_padded);
       return r;
     }
     case ConvRoute::ColSmallK:
@@ -3382,7 +3410,14 @@ torch::Tensor conv_wgrad_patch(torch::Tensor gy, torch::Tensor x,
                                int64_t S,
                                c10::optional<torch::Tensor> x_padded) {
   check_cl(gy, "conv_wgrad_patch gy");
-  check_cl(x, "conv_wgrad_patch x");
+  // with x_padded, x gives the shape only and may be any 4-D tensor (the
+  // fused BN/quantise route passes a strided view of the padded buffer)
+  const bool have_xp = x_padded.has_value() && x_padded->numel() > 0;
+  if (have_xp) {
+    TORCH_CHECK(x.dim() == 4, "conv_wgrad_patch x: expected a 4-D tensor");
+  } else {
+    check_cl(x, "conv_wgrad_patch x");
+  }
   TORCH_CHECK(x.element_size() == 2, "conv_wgrad_patch: 16-bit only");
   int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   int64_t K = gy.size(1), OH = gy.size(2), OW = gy.size(3);
@@ -3391,9 +3426,8 @@ torch::Tensor conv_wgrad_patch(torch::Tensor gy, torch::Tensor x,
   int64_t CRSp = R * S * Cp;
 
   // raw NHWC views (zero-copy for channels_last)
-  auto x2 = x.permute({0, 2, 3, 1}).reshape({N * H * W, C});
   torch::Tensor xp;
-  if (x_padded.has_value() && x_padded->numel() > 0) {
+  if (have_xp) {
     // the forward's channel-padded copy of x
     TORCH_CHECK(x_padded->dim() == 2 && x_padded->size(0) == N * H * W &&
                     x_padded->size(1) == Cp && x_padded->is_contiguous() &&
@@ -3402,6 +3436,7 @@ torch::Tensor conv_wgrad_patch(torch::Tensor gy, torch::Tensor x,
                 "conv_wgrad_patch: x_padded must be [N*H*W, round8(C)]");
     xp = *x_padded;
   } else {
+    auto x2 = x.permute({0, 2, 3, 1}).reshape({N * H * W, C});
     xp = (Cp == C) ? x2.contiguous() : pad_cols8(x2.contiguous(), Cp);
   }
   auto gy2 = gy.permute({0, 2, 3, 1}).reshape({M, K});

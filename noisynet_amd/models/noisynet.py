@@ -25,6 +25,18 @@ the un-pooled activation never exists and ``model.conv1_`` is None; only the
 introspective path and the L2_act/L3_act penalties read it, and those never
 take the fused-pool path. NOISYNET_NO_CONV1_POOL=1 selects the composition.
 
+bn1 -> relu -> clip -> quantize2 -> conv2: in steady state (training, 16-bit
+on the GPU, single-rank BN, no conv dropout, q_a2 > 0, current2 > 0, no
+crossbar mode, i >= 20, quantize2 calibrated to a fixed range from 0) the hot
+path runs ops.bn_act_quant: after the BN statistics ONE kernel reads the
+pooled conv1 output and writes the activation (for the backward kernels), the
+quantised activation already channel-padded the way conv2's kernel stages it,
+and its maximum (conv2's input_max). The unpadded quantised tensor of the
+composition (bn_act -> fake_quant -> max -> pad) is never stored; the backward
+is the composition's own. Values, gradients, running statistics, the seed
+sequence and quantize2.last_range are bit-identical to the composition, which
+every other case takes unchanged; NOISYNET_NO_BN_QUANT_FUSE=1 forces it.
+
 Tiled crossbars (--xbar_rows N > 0): every layer's contraction is cut into
 blocks of N crossbar rows (the (r, s, c) filter order; the input index for a
 linear layer), each with its own current noise (if the layer's current > 0)
@@ -205,10 +217,30 @@ class Net(nn.Module):
                 and getattr(a, 'L3_new', 0) == 0
                 and ops.conv_pool_eligible(x, self.conv1.weight))
 
+    def _bn_quant_range(self, x, i):
+        """quantize2's (min, max, stochastic) when bn1 + quantize2 + conv2 run
+        through ops.bn_act_quant (see module docstring), else None."""
+        import os
+        a = self.args
+        if not (self.training and a.batchnorm and i >= 20
+                and self.xbar_rows == 0 and a.q_a2 > 0 and a.current2 > 0
+                and a.dropout_conv == 0
+                and not getattr(a, 'sync_bn', False)
+                and not self.quantize2.calculate_running
+                and not os.environ.get('NOISYNET_NO_BN_QUANT_FUSE')
+                and ops.bn_act_quant_native(x, self.bn1.running_mean, 0.0)):
+            return None
+        rng = self.quantize2.quant_range()
+        if rng is None or rng[0] != 0:
+            return None
+        return rng
+
     def _noisy_layer_fused(self, x, layer, current, merged_dac, i, layer_num,
-                           is_conv, pool=False):
+                           is_conv, pool=False, x_pad=None, input_max=None):
         """One fused pass: quantized-weight conv/GEMM + sigma + noise
-        (+ the following 2x2 max-pool when ``pool``)."""
+        (+ the following 2x2 max-pool when ``pool``). ``x_pad`` / ``input_max``
+        come from ops.bn_act_quant: the channel-padded input the conv runs on
+        and max(x), which is then not reduced again."""
         a = self.args
         w_raw = layer.weight
         wq, bias = layer.effective_weight()
@@ -224,7 +256,8 @@ class Net(nn.Module):
                 power_denom = (x.detach().max() * w_max if want_telemetry
                                else w_max)
             else:
-                input_max = x.detach().max()
+                if input_max is None:
+                    input_max = x.detach().max()
                 factor = 0.1 * input_max / current
                 sigma_mode = 'abs2'
                 power_denom = input_max
@@ -232,10 +265,11 @@ class Net(nn.Module):
         if is_conv:
             conv = ops.fused_noisy_conv2d_pool if pool \
                 else ops.fused_noisy_conv2d
+            extra = {} if x_pad is None else {'x_pad': x_pad}
             out = conv(
                 x, wq, w_raw.detach(), bias, 1, 0, sigma_mode, factor,
                 current=current, power_denom=power_denom,
-                want_telemetry=want_telemetry, telemetry_out=telem)
+                want_telemetry=want_telemetry, telemetry_out=telem, **extra)
         else:
             out = ops.fused_noisy_linear(
                 x, wq, w_raw.detach(), bias, sigma_mode, factor,
@@ -361,16 +395,31 @@ class Net(nn.Module):
                 x = self.conv1(x)
             self.conv1_ = x
             x = ops.maxpool2x2(x)
-        if args.batchnorm:
-            x = self._bn_act(x, self.bn1, args.act_max1)
+        q2 = self._bn_quant_range(x, i)
+        if q2 is not None:
+            # bn1 + relu + clip + quantize2 (+ conv2's channel padding and
+            # input_max) as one kernel each way
+            bn = self.bn1
+            x, x_pad, x_max = ops.bn_act_quant(
+                x, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                bn.momentum, bn.eps, args.act_max1, args.q_a2, q2[0], q2[1],
+                q2[2], c_pad=ops.conv_input_pad_width(x, self.conv2.weight))
+            x = self._noisy_layer_fused(x, self.conv2, args.current2, False,
+                                        i, 1, True, x_pad=x_pad,
+                                        input_max=x_max)
         else:
-            x = ops.relu_clip(x, args.act_max1)
-        if args.dropout_conv > 0:
-            x = ops.dropout(x, args.dropout_conv, self.training)
-        if args.q_a2 > 0:
-            x = self.quantize2(x)
+            if args.batchnorm:
+                x = self._bn_act(x, self.bn1, args.act_max1)
+            else:
+                x = ops.relu_clip(x, args.act_max1)
+            if args.dropout_conv > 0:
+                x = ops.dropout(x, args.dropout_conv, self.training)
+            if args.q_a2 > 0:
+                x = self.quantize2(x)
 
-        if xbar:
+        if q2 is not None:
+            pass
+        elif xbar:
             x = self._xbar_layer(x, self.conv2, args.current2, False, i, 1,
                                  True)
         elif args.current2 > 0:

@@ -156,8 +156,10 @@ def _conv_wgrad_raw(g, x, stride, padding, w_shape, col=None):
     if use_native(g, x):
         R, S = w_shape[2], w_shape[3]
         if _is_padded_input(col, x):
-            # the noisy patch forward already padded x's channels to 8
-            return ext().conv_wgrad_patch(_nhwc(g), _nhwc(x), stride,
+            # the noisy patch forward already padded x's channels to 8 (or
+            # bn_act_quant wrote them padded): x gives the shape only, and
+            # may be a strided view of that padded buffer
+            return ext().conv_wgrad_patch(_nhwc(g), x, stride,
                                           padding, R, S, col)
         if col is not None and R * S > 1 \
                 and not _os.environ.get("NOISYNET_WGRAD_NO_COL"):
@@ -289,21 +291,28 @@ class _FusedNoisyConv(torch.autograd.Function):
         out    = y + eps * sqrt(factor * sigma),  eps ~ N(0,1) in-kernel
     Gradients flow through y only (noise is a detached additive term):
     hardware_model.py:23 wraps all noise math in no_grad.
+
+    ``x_pad``: the [N*H*W, round8(C)] channel-padded input that bn_act_quant
+    wrote; the kernel runs on it as it is and ``x`` (a view of it) is read for
+    its shape only, in forward and backward.
     """
 
     @staticmethod
     def forward(ctx, x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
-                want_telemetry, telemetry_out, current, power_denom):
+                want_telemetry, telemetry_out, current, power_denom,
+                x_pad=None):
         ctx.stride, ctx.padding = stride, padding
         ctx.has_bias = bias is not None
         col = None
+        if x_pad is not None and not use_native(x, wq):
+            raise ValueError("fused_noisy_conv2d: x_pad is a GPU-route argument")
         if use_native(x, wq):
             y, tele, col = ext().conv_fwd_fused(
-                _nhwc(x), _nhwc(wq), _nhwc(w_raw),
+                x if x_pad is not None else _nhwc(x), _nhwc(wq), _nhwc(w_raw),
                 bias if bias is not None else torch.empty(0, device=x.device, dtype=x.dtype),
                 stride, padding, 1 if sigma_mode == "abs" else 2,
                 _factor_tensor(factor, x.device), _next_seed(x.device),
-                bool(want_telemetry))
+                bool(want_telemetry), x_pad)
             if want_telemetry:
                 sum_sigma_abs = tele[0] / x.shape[0]
                 sum_abs_noise = tele[1] / y.numel()
@@ -347,15 +356,15 @@ class _FusedNoisyConv(torch.autograd.Function):
             gw = ConvWgrad.apply(g, x, ctx.stride, ctx.padding, wq.shape, col)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum(dim=(0, 2, 3))
-        return (gx, gw, None, gb) + (None,) * 8
+        return (gx, gw, None, gb) + (None,) * 9
 
 
 def fused_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode,
                        factor, current=0.0, power_denom=1.0,
-                       want_telemetry=False, telemetry_out=None):
+                       want_telemetry=False, telemetry_out=None, x_pad=None):
     return _FusedNoisyConv.apply(x, wq, w_raw, bias, stride, padding,
                                  sigma_mode, factor, want_telemetry,
-                                 telemetry_out, current, power_denom)
+                                 telemetry_out, current, power_denom, x_pad)
 
 
 # ---- noisy conv fused with its 2x2 max-pool (small-C image convs) ---------
@@ -1116,6 +1125,114 @@ def bn_act(x, weight, bias, running_mean, running_var, training, momentum,
            eps, relu=True, act_max=0.0, sync=False):
     return BnAct.apply(x, weight, bias, running_mean, running_var, training,
                        momentum, eps, relu, act_max, sync)
+
+
+# ---------------------------------------------------------------------------
+# Fused BatchNorm + ReLU + clip + fake-quant (+ channel padding, + max)
+# ---------------------------------------------------------------------------
+
+
+def conv_input_pad_width(x, w, padding=0):
+    """Channel count of the padded input copy the noisy conv of ``x`` with
+    ``w`` (stride 1) runs on: round8(C) where conv_fwd_fused's patch route
+    pads a 16-bit input with C % 8 != 0 itself, else C (no padded copy)."""
+    C = x.shape[1]
+    if (C % 8 == 0 or not use_native(x, w) or x.element_size() != 2
+            or _os.environ.get("NOISYNET_CONV_PAD_SHARE") == "0"):
+        return C
+    route = ext().conv_fused_route(C, x.shape[2], x.shape[3], w.shape[0],
+                                   w.shape[2], w.shape[3], 1, padding,
+                                   x.element_size())
+    return (C + 7) // 8 * 8 if route == "patch" else C
+
+
+def bn_act_quant_native(x, running_mean, min_value):
+    """Whether bn_act_quant runs its single-kernel forward on ``x``: a 16-bit
+    GPU tensor with numel % 4 == 0 (the composition quantises other sizes
+    with its scalar kernel, whose roundings the fused kernel does not
+    reproduce) and an unsigned range."""
+    return (use_native(x) and x.dtype in (torch.bfloat16, torch.float16)
+            and x.dim() in (2, 4) and x.numel() > 0 and x.numel() % 4 == 0
+            and (running_mean is None or running_mean.dtype == torch.float32)
+            and float(min_value) == 0.0)
+
+
+class BnActQuant(torch.autograd.Function):
+    """Training-mode BN + ReLU + clip + fake-quant with ONE forward kernel
+    (csrc/bn_act_quant.hip), bit-identical to bn_act -> fake_quant -> max().
+
+    Forward: bn_stats_finalize, then one pass that reads x and writes the
+    activation (kept for backward), the quantised tensor with its channels
+    zero-padded to ``c_pad``, and its maximum. No unpadded quantised tensor
+    is stored: the first output is a [N, C, H, W] view of the padded buffer
+    (x's own layout when c_pad == C). Backward is the composition's own pair
+    of kernels, ste_mask then bn_act_bwd, on the saved activation."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum,
+                eps, act_max, num_bits, min_value, max_value, stochastic,
+                c_pad):
+        xc = _nhwc(x) if x.dim() == 4 else x.contiguous()
+        empty = torch.empty(0, device=x.device, dtype=torch.float32)
+        mean, invstd = ext().bn_stats_finalize(
+            xc,
+            running_mean if running_mean is not None else empty,
+            running_var if running_var is not None else empty,
+            float(momentum), float(eps))
+        # the seed is drawn where fake_quant draws its own, so every later
+        # layer sees the same seed sequence as on the composition
+        act, xq_pad, xmax = ext().bn_act_quant_fwd(
+            xc, mean, invstd, weight.float().contiguous(),
+            bias.float().contiguous(), True, float(act_max), int(num_bits),
+            float(min_value), float(max_value), float(stochastic),
+            _next_seed(x.device), int(c_pad))
+        C = x.shape[1]
+        if x.dim() == 4:
+            N, _, H, W = x.shape
+            xq = xq_pad.view(N, H, W, c_pad)[..., :C].permute(0, 3, 1, 2)
+        else:
+            xq = xq_pad[:, :C]
+        xmax = xmax.to(x.dtype).reshape(())
+        ctx.save_for_backward(xc, weight, mean, invstd, act)
+        ctx.act_max = float(act_max)
+        ctx.q_range = (float(min_value), float(max_value))
+        ctx.mark_non_differentiable(xq_pad, xmax)
+        return xq, xq_pad, xmax
+
+    @staticmethod
+    def backward(ctx, g, _g_pad, _g_max):
+        x, weight, mean, invstd, act = ctx.saved_tensors
+        gq = ext().ste_mask(g, act, ctx.q_range[0], ctx.q_range[1])
+        gx, g_gamma, g_beta = ext().bn_act_bwd(
+            gq, x, act, mean, invstd, weight.float().contiguous(), True, True,
+            ctx.act_max)
+        return (gx, g_gamma.to(weight.dtype),
+                g_beta.to(weight.dtype)) + (None,) * 10
+
+
+def bn_act_quant(x, weight, bias, running_mean, running_var, momentum, eps,
+                 act_max, num_bits, min_value, max_value, stochastic=0.0,
+                 c_pad=None):
+    """Training-mode ``fake_quant(bn_act(x, relu=True, act_max))`` and its
+    maximum. Returns ``(xq, x_pad, xq_max)``.
+
+    Tensors that pass bn_act_quant_native take BnActQuant: ``x_pad`` is
+    the [rows, c_pad] channel-padded quantised tensor (None when ``c_pad`` is
+    None or C) and ``xq`` a view of it; hand both to fused_noisy_conv2d.
+    ``c_pad`` comes from conv_input_pad_width. Everything else (CPU, fp32, a
+    signed range, numel % 4 != 0) is the composition of the two ops, with
+    ``x_pad`` None."""
+    C = x.shape[1]
+    if bn_act_quant_native(x, running_mean, min_value):
+        c_pad = C if c_pad is None else int(c_pad)
+        xq, xq_pad, xmax = BnActQuant.apply(
+            x, weight, bias, running_mean, running_var, momentum, eps,
+            act_max, num_bits, min_value, max_value, stochastic, c_pad)
+        return xq, (xq_pad if c_pad != C else None), xmax
+    y = bn_act(x, weight, bias, running_mean, running_var, True, momentum,
+               eps, relu=True, act_max=act_max)
+    xq = fake_quant(y, num_bits, min_value, max_value, stochastic)
+    return xq, None, xq.detach().max()
 
 
 # ---------------------------------------------------------------------------

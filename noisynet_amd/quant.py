@@ -89,11 +89,20 @@ class QuantMeasure(nn.Module):
         self._range_cache = None
         return super()._load_from_state_dict(*args, **kwargs)
 
-    def forward(self, input):
+    def quant_range(self, input=None):
+        """The range decision of one forward call: ``(min_value, max_value,
+        stochastic)`` as forward hands them to the quantiser, with the same
+        side effects (calibration lists, the range cache, ``last_range``).
+
+        A caller that fuses the quantiser into another kernel asks without an
+        ``input``; the answer is then None, with no side effect, whenever the
+        decision needs the data (calibration, or no fixed range yet)."""
         with torch.no_grad():
             min_value = self.min_value
             max_value = self.max_value
             if self.calculate_running:
+                if input is None:
+                    return None
                 if self.min_value < 0:  # weights: separate pos/neg percentiles
                     pos = input[input > 0]
                     neg = input[input < 0].abs()
@@ -126,6 +135,8 @@ class QuantMeasure(nn.Module):
                 elif float(self.running_max) > 0:
                     max_value = float(self.running_max)
                 else:
+                    if input is None:
+                        return None
                     max_value = input.max().item()  # data-dependent
                     cacheable = False
                 if cacheable:
@@ -135,7 +146,10 @@ class QuantMeasure(nn.Module):
             # the floats this call quantises with (bit-serial crossbar inputs
             # derive the activation LSB from them)
             self.last_range = (float(min_value), float(max_value))
+        return min_value, max_value, stoch
 
+    def forward(self, input):
+        min_value, max_value, stoch = self.quant_range(input)
         return ops.fake_quant(input, self.num_bits, min_value, max_value, stoch)
 
 
