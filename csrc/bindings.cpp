@@ -197,6 +197,20 @@ std::vector<torch::Tensor> xbar_serial_fwd_linear(
     int64_t adc_bits, torch::Tensor adc, int64_t in_bits, int64_t dac_bits,
     torch::Tensor dac, int64_t seed, bool telem);
 
+// bit-sliced weights: w_bits-bit offset-binary codes on the grid
+// w_min + code * w_step, cell_bits per column, unipolar per-column ADCs;
+// cell = fp32 [w_step, 1/w_step, w_min]
+std::vector<torch::Tensor> xbar_cells_fwd_conv(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor bias, int64_t stride,
+    int64_t pad, int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
+    int64_t adc_bits, torch::Tensor adc, int64_t w_bits, int64_t cell_bits,
+    torch::Tensor cell, int64_t seed, bool telem);
+std::vector<torch::Tensor> xbar_cells_fwd_linear(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor bias, int64_t sigma_mode,
+    torch::Tensor factor, int64_t xbar_rows, int64_t adc_bits,
+    torch::Tensor adc, int64_t w_bits, int64_t cell_bits, torch::Tensor cell,
+    int64_t seed, bool telem);
+
 std::string conv_fused_route(int64_t C, int64_t H, int64_t W, int64_t K,
                              int64_t R, int64_t S, int64_t stride, int64_t pad,
                              int64_t elem_size);
@@ -273,4 +287,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xbar_diff_fwd_linear", &xbar_diff_fwd_linear);
   m.def("xbar_serial_fwd_conv", &xbar_serial_fwd_conv);
   m.def("xbar_serial_fwd_linear", &xbar_serial_fwd_linear);
+  m.def("xbar_cells_fwd_conv", &xbar_cells_fwd_conv);
+  m.def("xbar_cells_fwd_linear", &xbar_cells_fwd_linear);
 }

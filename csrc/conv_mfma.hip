@@ -4428,6 +4428,286 @@ void xbar_serial_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Bit-sliced weights: a cell holds E bits, so the B-bit weight code (offset
+// binary on the weight quantiser's grid w = w_min + code * w_step) is spread
+// over NSLICE = ceil(B / E) columns. Every column of every block has its own
+// current, noise draw and UNIPOLAR ADC conversion; the digital side shift-adds
+// the columns and adds the offset w_min * sum x.
+//   code = clamp(rint((f32(wq) - w_min) * inv_w_step), 0, 2^B - 1)
+//   d_t  = (code >> t*E) & (2^E - 1)                       t = 0..NSLICE-1
+//   p_bt = w_step * sum x * d_t
+//   s_bt = max(p_bt, 0)                                    (abs: g = w_step d)
+//        = max(w_step^2 * sum x * d_t^2 + p_bt, 0)         (abs2: g^2 + g)
+//   v_bt = p_bt + eps_bt * sqrt(factor * s_bt)
+//   q_bt = step * clamp(rint(v_bt * inv_step), 0, Qu)
+//   X_b  = sum x
+//   out  = sum_b (sum_t 2^(tE) q_bt + w_min * X_b) + bias
+// (b ascending, t ascending inside b, the offset after the block's columns).
+// The MFMA operands are the activation and the integers d_t, d_t^2 <= 225
+// (exact in every dtype); w_step and w_step^2 multiply the fp32 accumulators
+// in the epilogue, so abs mode needs no sigma MFMA at all; neither does abs2
+// with one-bit cells, where d_t^2 = d_t: the host then launches the abs
+// instantiation with ``fold_squares`` set and the epilogue adds
+// w_step^2 * sum x * d_t from the one accumulator. The staging thread
+// derives the code once from its 8 wq elements and writes NSLICE digit tiles
+// (and NSLICE tiles of d_t^2 with abs2); the activation tile is staged once
+// per k-step and serves every column. X_b is one MFMA per fm against an
+// all-ones B fragment held in registers: every column of the result is the
+// row sum, so it serves both fn. w_raw is not read: the conductances are the
+// digits. The Philox counter of a four-row group is
+// ((b*NSLICE + t)*M + m)*K + k: with one slice, w_step 1 and w_min 0 this
+// kernel draws what xbar_fwd_kernel draws. Bias is a run-time branch.
+// ---------------------------------------------------------------------------
+
+// TELEM: telem[5] = sum_bt p_bt (the current the cells draw, NOT
+//        shift-weighted), sum |sum_bt 2^(tE) noise_bt|, max clean shift-added
+//        y with the offset and the bias, (unused, see sat_count), max |v_bt|;
+//        sat_count = number of (b, t) partials with rint(v_bt / step) > Qu
+//        or < 0
+template <typename T, int NSLICE, int SIGMA_MODE, bool ADC, bool TELEM>
+__global__ __launch_bounds__(kBlock)
+void xbar_cells_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
+                           const float* __restrict__ bias,
+                           T* __restrict__ out, ConvGeom g, int wpitch,
+                           int xbar_rows, int w_bits, int cell_bits,
+                           int fold_squares /* abs2 on one-bit cells */,
+                           const float* __restrict__ cell_p /* w_step, 1/w_step, w_min */,
+                           const float* __restrict__ factor_p,
+                           const float* __restrict__ adc_p /* step, 1/step */,
+                           float qu, uint64_t seed, float* __restrict__ telem,
+                           unsigned long long* __restrict__ sat_count,
+                           const int64_t* __restrict__ seed_base) {
+  seed = graph_seed(seed_base, seed);
+  const float factor = (SIGMA_MODE > 0) ? factor_p[0] : 0.0f;
+  const float step = ADC ? adc_p[0] : 1.0f;
+  const float inv_step = ADC ? adc_p[1] : 1.0f;
+  const float w_step = cell_p[0];
+  const float inv_w_step = cell_p[1];
+  const float w_min = cell_p[2];
+  const float w_step2 = __fmul_rn(w_step, w_step);
+  // SIGMA_MODE 1: s = sq1 * sum x * d_t + p_bt with sq1 = 0 (abs, s = p_bt
+  // exactly) or w_step^2 (abs2 on one-bit cells)
+  const float sq1 = fold_squares ? w_step2 : 0.0f;
+  const float code_max = (float)((1 << w_bits) - 1);
+  const int dmask = (1 << cell_bits) - 1;
+  int n0 = blockIdx.x * BN;
+  int64_t m0 = (int64_t)blockIdx.y * BM;
+
+  constexpr int STR = Mma<T>::STRIDE;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* a_lds = smem;                               // BM rows (x)
+  char* d_lds = smem + BM * STR;                    // NSLICE x BN rows (d_t)
+  char* e_lds = smem + (BM + NSLICE * BN) * STR;    // NSLICE x BN rows (d_t^2)
+
+  int wid = threadIdx.x / WAVE;
+  int wm = wid >> 1, wn = wid & 1;
+  int lane = threadIdx.x & (WAVE - 1);
+
+  XbarRow xr;
+  {
+    int64_t sm = m0 + (threadIdx.x >> 2);
+    xr.live = sm < g.M;
+    int oh = 0, ow = 0;
+    xr.img = 0;
+    if (xr.live) {
+      int64_t t = sm;
+      ow = (int)(t % g.OW); t /= g.OW;
+      oh = (int)(t % g.OH); t /= g.OH;
+      xr.img = (int)t;
+    }
+    xr.ih0 = oh * g.stride - g.pad;
+    xr.iw0 = ow * g.stride - g.pad;
+    xr.r = xr.s = xr.c = 0;
+    xbar_row_advance(xr, g, (threadIdx.x & 3) * 8);
+  }
+
+  typename Mma<T>::frag ones;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ones[e] = 1.0f;
+
+  f32x4 acc[NSLICE][2][2] = {};    // sum x * d_t of the block
+  f32x4 sacc[NSLICE][2][2] = {};   // sum x * d_t^2 of the block (abs2)
+  f32x4 xacc[2] = {};              // X_b = sum x of the block, per fm
+  f32x4 oacc[2][2] = {};           // sum_b (sum_t 2^(tE) q_bt + w_min X_b)
+  f32x4 ycl[2][2] = {};            // the same with p_bt for q_bt (telemetry)
+  f32x4 ntot[2][2] = {};           // sum_bt 2^(tE) noise_bt (telemetry)
+  float t_sum_sigma = 0.0f, t_sat = 0.0f, t_vmax = 0.0f;
+
+  const int nrows = g.R * g.S * g.C;
+  const int steps_per_block = xbar_rows / BK;
+  int steps_left = steps_per_block;
+  int b = 0;
+  XbarRegs<T> rg;   // rg.w stays unused: the conductances are the digits
+  xbar_load_x(rg.x, x, g, xr);
+  xbar_load_w<T, 0>(rg.q, rg.w, wq, wq, g.K, n0, 0, nrows, wpitch);
+  for (int ck = 0; ck < nrows; ck += BK) {
+    {
+      // the code, once; then one digit tile (and one of squares) per slice.
+      // Rows past the contraction or past K stage the code of a zero weight:
+      // their activations are zero / their outputs are never stored
+      int row = threadIdx.x >> 2;
+      int seg = threadIdx.x & 3;
+      xbar_put8<T>(a_lds, row, seg, rg.x);
+      int code[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float c = rintf((to_f32(rg.q[e]) - w_min) * inv_w_step);
+        code[e] = (int)fminf(fmaxf(c, 0.0f), code_max);
+      }
+#pragma unroll
+      for (int t = 0; t < NSLICE; ++t) {
+        float d[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          d[e] = (float)((code[e] >> (t * cell_bits)) & dmask);
+        Mma<T>::store8(d_lds + t * BN * STR, row, seg * 8, d);
+        if (SIGMA_MODE == 2) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) d[e] *= d[e];
+          Mma<T>::store8(e_lds + t * BN * STR, row, seg * 8, d);
+        }
+      }
+    }
+    __syncthreads();
+    if (ck + BK < nrows) {  // next step's loads, in flight under the MFMAs
+      xbar_row_advance(xr, g, BK);
+      xbar_load_x(rg.x, x, g, xr);
+      xbar_load_w<T, 0>(rg.q, rg.w, wq, wq, g.K, n0, ck + BK, nrows, wpitch);
+    }
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm) {
+      auto a = Mma<T>::load(a_lds, wm * 32 + fm * 16 + (lane & 15), lane);
+      Mma<T>::mma(a, ones, xacc[fm]);
+#pragma unroll
+      for (int fn = 0; fn < 2; ++fn) {
+        int brow = wn * 32 + fn * 16 + (lane & 15);
+#pragma unroll
+        for (int t = 0; t < NSLICE; ++t) {
+          auto bd = Mma<T>::load(d_lds + t * BN * STR, brow, lane);
+          Mma<T>::mma(a, bd, acc[t][fm][fn]);
+          if (SIGMA_MODE == 2) {
+            auto be = Mma<T>::load(e_lds + t * BN * STR, brow, lane);
+            Mma<T>::mma(a, be, sacc[t][fm][fn]);
+          }
+        }
+      }
+    }
+    __syncthreads();
+
+    if (--steps_left > 0 && ck + BK < nrows) continue;
+    // block boundary (or the end): NSLICE noise draws and NSLICE unipolar
+    // ADCs on the live fragments, shift-added; then the block's offset
+    steps_left = steps_per_block;
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm) {
+#pragma unroll
+      for (int fn = 0; fn < 2; ++fn) {
+        int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
+        int n = n0 + wn * 32 + fn * 16 + (lane & 15);
+#pragma unroll
+        for (int t = 0; t < NSLICE; ++t) {
+          const float shift = (float)(1 << (t * cell_bits));
+          float g4[4];
+          if (SIGMA_MODE > 0)
+            gauss4(seed,
+                   (uint64_t)((((int64_t)b * NSLICE + t) * g.M + mb) * g.K + n),
+                   g4);
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            bool inside = mb + reg < g.M && n < g.K;
+            float p = __fmul_rn(w_step, acc[t][fm][fn][reg]);
+            float v = p;
+            if (SIGMA_MODE > 0) {
+              float sig = (SIGMA_MODE == 2)
+                  ? __fadd_rn(__fmul_rn(w_step2, sacc[t][fm][fn][reg]), p)
+                  : __fadd_rn(__fmul_rn(sq1, acc[t][fm][fn][reg]), p);
+              sig = fmaxf(sig, 0.0f);
+              float noise = g4[reg] * sqrtf(factor * sig);
+              v = p + noise;
+              if (TELEM) {
+                ntot[fm][fn][reg] += shift * noise;
+                if (inside) t_sum_sigma += p;
+              }
+            }
+            float q = v;
+            if (ADC) {
+              float c = rintf(v * inv_step);
+              if (TELEM && inside && (c > qu || c < 0.0f)) t_sat += 1.0f;
+              q = step * fminf(fmaxf(c, 0.0f), qu);
+            }
+            if (TELEM) {
+              ycl[fm][fn][reg] += shift * p;
+              if (inside) t_vmax = fmaxf(t_vmax, fabsf(v));
+            }
+            oacc[fm][fn][reg] += shift * q;
+          }
+          acc[t][fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+          sacc[t][fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          float off = __fmul_rn(w_min, xacc[fm][reg]);
+          oacc[fm][fn][reg] = __fadd_rn(oacc[fm][fn][reg], off);
+          if (TELEM) ycl[fm][fn][reg] = __fadd_rn(ycl[fm][fn][reg], off);
+        }
+      }
+      xacc[fm] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    ++b;
+  }
+
+  // bias, the one rounding to the dtype, stores
+  float t_sum_noise = 0.0f, t_max_y = -INFINITY;
+#pragma unroll
+  for (int fm = 0; fm < 2; ++fm) {
+#pragma unroll
+    for (int fn = 0; fn < 2; ++fn) {
+      int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
+      int n = n0 + wn * 32 + fn * 16 + (lane & 15);
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        int64_t m = mb + reg;
+        if (m < g.M && n < g.K) {
+          float bv = bias ? bias[n] : 0.0f;
+          out[m * g.K + n] = from_f32<T>(oacc[fm][fn][reg] + bv);
+          if (TELEM) {
+            t_sum_noise += fabsf(ntot[fm][fn][reg]);
+            t_max_y = fmaxf(t_max_y, ycl[fm][fn][reg] + bv);
+          }
+        }
+      }
+    }
+  }
+  if (TELEM) {
+    __shared__ float red[4];
+    __shared__ float redm[2][4];
+    float s0 = block_sum(t_sum_sigma, red);
+    __syncthreads();
+    float s1 = block_sum(t_sum_noise, red);
+    __syncthreads();
+    float s3 = block_sum(t_sat, red);  // <= NSLICE * nblocks * 4096: exact
+    float my = wave_max(t_max_y);
+    float mv = wave_max(t_vmax);
+    if (lane == 0) {
+      redm[0][wid] = my;
+      redm[1][wid] = mv;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      if (SIGMA_MODE > 0) {
+        atomicAdd(&telem[0], s0);
+        atomicAdd(&telem[1], s1);
+      }
+      atomic_max_f32(&telem[2], fmaxf(fmaxf(redm[0][0], redm[0][1]),
+                                      fmaxf(redm[0][2], redm[0][3])));
+      if (ADC) atomicAdd(sat_count, (unsigned long long)(s3 + 0.5f));
+      atomic_max_f32(&telem[4], fmaxf(fmaxf(redm[1][0], redm[1][1]),
+                                      fmaxf(redm[1][2], redm[1][3])));
+    }
+  }
+}
+
 void check_xbar_args(int64_t sigma_mode, int64_t xbar_rows, int64_t adc_bits,
                      const torch::Tensor& adc, const torch::Tensor& x,
                      const char* who) {
@@ -4696,7 +4976,167 @@ std::vector<torch::Tensor> xbar_serial_fwd_impl(
   return {out, tele};
 }
 
+// slice count of a bit-sliced-weight call, after checking w_bits / cell_bits
+// / cell
+int check_xbar_cells_args(int64_t w_bits, int64_t cell_bits,
+                          const torch::Tensor& cell, const torch::Tensor& x,
+                          const char* who) {
+  TORCH_CHECK(cell_bits >= 1 && cell_bits <= 4, who,
+              ": cell_bits must be 1..4, got ", cell_bits);
+  TORCH_CHECK(w_bits >= 1 && w_bits <= 8, who, ": w_bits must be 1..8, got ",
+              w_bits);
+  int64_t slices = (w_bits + cell_bits - 1) / cell_bits;
+  TORCH_CHECK(slices <= 4, who, ": w_bits ", w_bits, " at cell_bits ",
+              cell_bits, " is ", slices, " slices, at most 4 are built; the "
+              "smallest cell_bits that works is ", (w_bits + 3) / 4);
+  TORCH_CHECK(cell.numel() == 3 && cell.scalar_type() == torch::kFloat32 &&
+                  cell.is_contiguous() && cell.device() == x.device(),
+              who, ": cell must be the fp32 device tensor "
+              "[w_step, 1/w_step, w_min]");
+  return (int)slices;
+}
+
+// as xbar_fwd_impl, for xbar_cells_fwd_kernel (no w_raw)
+std::vector<torch::Tensor> xbar_cells_fwd_impl(
+    const torch::Tensor& x, torch::Tensor wq2, const torch::Tensor& bias,
+    ConvGeom g, torch::Tensor out, int64_t sigma_mode,
+    const torch::Tensor& factor, int64_t xbar_rows, int64_t adc_bits,
+    const torch::Tensor& adc, int64_t w_bits, int64_t cell_bits,
+    const torch::Tensor& cell, int64_t seed, bool telem, const char* who) {
+  check_xbar_args(sigma_mode, xbar_rows, adc_bits, adc, x, who);
+  const int NS = check_xbar_cells_args(w_bits, cell_bits, cell, x, who);
+  int nrows = g.R * g.S * g.C;
+  TORCH_CHECK(wq2.dim() == 2 && wq2.size(0) == g.K && wq2.size(1) == nrows,
+              who, ": weight shape mismatch");
+  TORCH_CHECK(wq2.scalar_type() == x.scalar_type(), who,
+              ": x and the weights must share one dtype");
+  int pitch = nrows;
+  if (x.element_size() == 2 && (nrows & 7) != 0) {
+    pitch = (nrows + 7) & ~7;
+    wq2 = at::constant_pad_nd(wq2, {0, pitch - nrows}, 0);
+  }
+  wq2 = wq2.contiguous();
+  bool has_bias = bias.numel() > 0;
+  if (has_bias) TORCH_CHECK(bias.numel() == g.K, who, ": bias size mismatch");
+  torch::Tensor bias_f;
+  if (has_bias) bias_f = bias.to(torch::kFloat32).contiguous();
+  auto f32 = x.options().dtype(torch::kFloat32);
+  torch::Tensor tele, sat;
+  if (telem) {
+    tele = torch::zeros({5}, f32);
+    tele[2] = -std::numeric_limits<float>::infinity();
+    sat = torch::zeros({1}, x.options().dtype(torch::kLong));
+  } else {
+    tele = torch::empty({0}, f32);
+  }
+  auto factor_f = factor.to(torch::kFloat32).reshape({1}).contiguous();
+  bool adc_on = adc_bits > 0;
+  float qu = adc_on ? (float)((1 << adc_bits) - 1) : 0.0f;   // unipolar
+  // one-bit digits are their own squares: abs2 runs on the abs instantiation
+  const int fold = (sigma_mode == 2 && cell_bits == 1) ? 1 : 0;
+  const int64_t kmode = fold ? 1 : sigma_mode;
+  dim3 grid((g.K + BN - 1) / BN, (int)((g.M + BM - 1) / BM));
+  NN_DISPATCH(x.scalar_type(), "xbar_cells_fwd", [&] {
+    using T = typename DevT<scalar_t>::type;
+    // x tile + NS digit tiles (+ NS tiles of squares with abs2): at most
+    // (64 + 8 * 64) * 80 = 46080 bytes for the 16-bit dtypes; fp32 with
+    // four slices and abs2 is 82944 bytes and opts in to the large LDS
+    size_t lds = (size_t)(BM + (kmode == 2 ? 2 : 1) * NS * BN)
+        * Mma<T>::STRIDE;
+    auto stream = c10::hip::getCurrentHIPStream();
+    const T* xp = (const T*)x.data_ptr();
+    const T* wqp = (const T*)wq2.data_ptr();
+    const float* bp = has_bias ? bias_f.data_ptr<float>() : nullptr;
+    T* op = (T*)out.data_ptr();
+    float* tp = telem ? tele.data_ptr<float>() : nullptr;
+    unsigned long long* sp =
+        telem ? (unsigned long long*)sat.data_ptr<int64_t>() : nullptr;
+    const float* f = factor_f.data_ptr<float>();
+    const float* ap = adc_on ? adc.data_ptr<float>() : nullptr;
+    const float* cp = cell.data_ptr<float>();
+    uint64_t sd = (uint64_t)seed;
+    auto launch = [&](auto ns, auto sm, auto ad, auto tl) {
+      auto kfn = xbar_cells_fwd_kernel<T, decltype(ns)::value,
+                                       decltype(sm)::value,
+                                       decltype(ad)::value,
+                                       decltype(tl)::value>;
+      if (lds > 65536)
+        TORCH_CHECK(hipFuncSetAttribute(
+                        (const void*)kfn,
+                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                        (int)lds) == hipSuccess,
+                    who, ": ", lds, " bytes of LDS are not available");
+      hipLaunchKernelGGL(kfn, grid, dim3(kBlock), lds, stream, xp, wqp, bp,
+                         op, g, pitch, (int)xbar_rows, (int)w_bits,
+                         (int)cell_bits, fold, cp, f, ap, qu, sd, tp, sp,
+                         g_seed_base);
+    };
+    using TT = std::true_type; using FF = std::false_type;
+    auto with_telem = [&](auto ns, auto sm, auto ad) {
+      if (telem) launch(ns, sm, ad, TT{}); else launch(ns, sm, ad, FF{});
+    };
+    auto with_adc = [&](auto ns, auto sm) {
+      if (adc_on) with_telem(ns, sm, TT{}); else with_telem(ns, sm, FF{});
+    };
+    auto with_mode = [&](auto ns) {
+      // check_xbar_args left exactly these: 0 (ADC on), 1, 2
+      if (kmode == 0)
+        with_telem(ns, std::integral_constant<int, 0>{}, TT{});
+      else if (kmode == 1) with_adc(ns, std::integral_constant<int, 1>{});
+      else with_adc(ns, std::integral_constant<int, 2>{});
+    };
+    if (NS == 1) with_mode(std::integral_constant<int, 1>{});
+    else if (NS == 2) with_mode(std::integral_constant<int, 2>{});
+    else if (NS == 3) with_mode(std::integral_constant<int, 3>{});
+    else with_mode(std::integral_constant<int, 4>{});
+  });
+  HIP_CHECK_LAST();
+  if (telem) tele.narrow(0, 3, 1).copy_(sat);
+  return {out, tele};
+}
+
 }  // namespace
+
+// bit-sliced weights (w_bits-bit offset-binary codes on the grid
+// w_min + code * w_step, cell_bits per column); cell = fp32
+// [w_step, 1/w_step, w_min]; adc is [step, 1/step] of the unipolar step
+// adc_max / (2^bits - 1)
+std::vector<torch::Tensor> xbar_cells_fwd_conv(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor bias, int64_t stride,
+    int64_t pad, int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
+    int64_t adc_bits, torch::Tensor adc, int64_t w_bits, int64_t cell_bits,
+    torch::Tensor cell, int64_t seed, bool telem) {
+  const char* who = "xbar_cells_fwd_conv";
+  check_cl(x, "xbar_cells_fwd_conv x");
+  check_cl(wq, "xbar_cells_fwd_conv wq");
+  TORCH_CHECK(wq.size(1) == x.size(1), who, ": channel mismatch");
+  auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
+                     (int)x.size(1), (int)wq.size(0), (int)wq.size(2),
+                     (int)wq.size(3), (int)stride, (int)pad);
+  TORCH_CHECK(g.OH > 0 && g.OW > 0, who, ": empty output");
+  auto out = torch::empty({g.N, g.K, g.OH, g.OW},
+                          x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  int64_t nrows = (int64_t)g.R * g.S * g.C;
+  auto wq2 = wq.permute({0, 2, 3, 1}).reshape({(int64_t)g.K, nrows});
+  return xbar_cells_fwd_impl(x, wq2, bias, g, out, sigma_mode, factor,
+                             xbar_rows, adc_bits, adc, w_bits, cell_bits,
+                             cell, seed, telem, who);
+}
+
+std::vector<torch::Tensor> xbar_cells_fwd_linear(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor bias, int64_t sigma_mode,
+    torch::Tensor factor, int64_t xbar_rows, int64_t adc_bits,
+    torch::Tensor adc, int64_t w_bits, int64_t cell_bits, torch::Tensor cell,
+    int64_t seed, bool telem) {
+  const char* who = "xbar_cells_fwd_linear";
+  TORCH_CHECK(wq.dim() == 2 && wq.size(1) == x.size(1), who,
+              ": weight shape mismatch");
+  auto g = linear_geom(x, wq.size(0));
+  auto out = torch::empty({x.size(0), wq.size(0)}, x.options());
+  return xbar_cells_fwd_impl(x, wq, bias, g, out, sigma_mode, factor,
+                             xbar_rows, adc_bits, adc, w_bits, cell_bits,
+                             cell, seed, telem, who);
+}
 
 // bit-serial inputs (in_bits-bit codes on the grid x_step, dac_bits per
 // slice); dac = fp32 [x_step, 1/x_step]

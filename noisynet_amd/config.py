@@ -125,6 +125,15 @@ def build_noisynet_parser():
                              'noise draw and ADC conversion, --adc_max is the '
                              'range of one slice (0 = all bits at once; needs '
                              '--xbar_rows and --q_a, at most 4 slices)')
+    parser.add_argument('--xbar_cell_bits', type=int, default=0, metavar='',
+                        help='bit-sliced crossbar weights: bits per cell, '
+                             '1..4; the q_w-bit offset-binary weight code is '
+                             'spread over ceil(q_w / bits) columns, each with '
+                             'its own noise draw and a unipolar ADC over '
+                             '[0, adc_max], --adc_max is the range of one '
+                             'slice (0 = one analog cell per weight; needs '
+                             '--xbar_rows and 0 < q_w < 8 on every layer, at '
+                             'most 4 slices)')
     return parser
 
 

@@ -352,15 +352,20 @@ def print_xbar_stats(model, args):
     --xbar_diff the clip share and the max are per column partial (W+ and W-
     columns, unipolar ADCs); with --xbar_dac_bits D they are per SLICE partial
     (J = ceil(q_a / D) conversions per tile and output), so the printed max is
-    the figure for the per-slice --adc_max."""
+    the figure for the per-slice --adc_max. With --xbar_cell_bits E they are
+    per cell slice partial (T = ceil(q_w / E) unipolar conversions per tile
+    and output); the printed max is again the per-slice --adc_max figure."""
     def mean(v):
         return float(np.mean(v)) if len(v) else float('nan')
 
     diff = getattr(args, 'xbar_diff', False)
     dac_bits = getattr(args, 'xbar_dac_bits', 0) or 0
+    cell_bits = getattr(args, 'xbar_cell_bits', 0) or 0
     clip_name = 'clipped per column' if diff else 'clipped'
     if dac_bits > 0:
         clip_name = 'clipped per slice'
+    if cell_bits > 0:
+        clip_name = 'clipped per cell slice'
     for k in range(args.num_layers):
         if not model.partial_absmax[k]:
             continue
@@ -369,6 +374,11 @@ def print_xbar_stats(model, args):
             q_a = getattr(args, 'q_a%d' % (k + 1))
             adc_kind = ('bit-serial inputs D={:d} J={:d}, per slice partial, '
                         .format(dac_bits, -(-q_a // dac_bits)))
+        if cell_bits > 0:
+            q_w = getattr(args, 'q_w%d' % (k + 1))
+            adc_kind = ('bit-sliced weights E={:d} T={:d}, per cell slice '
+                        'partial, unipolar ADC, '
+                        .format(cell_bits, -(-q_w // cell_bits)))
         print('\txbar layer {:d} ({:d} rows/tile, {}{:d}-bit ADC, '
               'adc_max {:g}):  power {:.3g}  NSR {:.3g}  {} {:.2%}  '
               'max|partial| {:.4g}'

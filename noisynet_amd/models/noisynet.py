@@ -61,6 +61,26 @@ comes from the range the preceding QuantMeasure quantised with (its
 unchanged (same cell current per unit input), so the MSB slice's noise enters
 the output times 2^((J-1)D). Not combinable with --xbar_diff; bf16 carries at
 most 7-bit codes. With --xbar_dac_bits 0 nothing changes.
+
+Bit-sliced weights (--xbar_cell_bits E in 1..4, with --xbar_rows): a cell
+holds E bits, so every crossbar layer spreads its q_w<k>-bit weight code over
+T = ceil(q_w/E) <= 4 columns (ops.xbar_noisy_*(..., w_bits, cell_bits, w_step,
+w_min)). The code is offset binary on the grid of the layer's weight quantiser,
+w = w_min + code * w_step with w_step = max((hi - lo) / (2^q_w - 1), 1e-6) and
+w_min = lo from its ``last_range``. Per tile b and slice t
+    p_bt = w_step * sum x * d_t              d_t = (code >> tE) & (2^E - 1)
+    v_bt = p_bt + eps_bt * sqrt(factor * s_bt),  s_bt = sum x * f(w_step * d_t)
+    q_bt = unipolar ADC of v_bt over [0, adc_max]
+    out  = sum_b (sum_t 2^(tE) q_bt + w_min * sum x) + bias
+Two consequences: offset-binary cells carry current even for a zero weight
+(code -w_min / w_step), so noise and power are higher than the signed
+one-cell model's; and --adc_max is a per-slice, unipolar figure, to be read
+off the printed max |partial| (``adc_clip`` / ``partial_absmax`` are per cell
+slice partial). Every layer needs 0 < q_w<k> < 8 (NoisyLinear leaves 8-bit
+weights unquantised) and a range whose codes the dtype carries:
+max(|lo|, |hi|) * u_dtype < w_step / 2. Not combinable with --xbar_diff,
+--xbar_dac_bits or the introspective flags. With --xbar_cell_bits 0 nothing
+changes.
 """
 
 import torch
@@ -147,6 +167,11 @@ class Net(nn.Module):
         if self.xbar_dac_bits > 0 and self.xbar_rows <= 0:
             raise ValueError('--xbar_dac_bits needs --xbar_rows > 0: bit-serial '
                              'inputs are a mode of the tiled crossbars')
+        self.xbar_cell_bits = getattr(args, 'xbar_cell_bits', 0) or 0
+        if self.xbar_cell_bits > 0 and self.xbar_rows <= 0:
+            raise ValueError('--xbar_cell_bits needs --xbar_rows > 0: '
+                             'bit-sliced weights are a mode of the tiled '
+                             'crossbars')
         if self.xbar_rows > 0:
             self._check_xbar_args()
 
@@ -202,6 +227,29 @@ class Net(nn.Module):
                         'most 4 are built; the smallest --xbar_dac_bits that '
                         'works is %d' % (D, k, q_a, -(-q_a // D),
                                          -(-q_a // 4)))
+        E = self.xbar_cell_bits = getattr(a, 'xbar_cell_bits', 0) or 0
+        if E < 0 or E > 4:
+            raise ValueError('--xbar_cell_bits must be 0 or 1..4, got %d' % E)
+        if E > 0:
+            if self.xbar_diff or D > 0:
+                raise ValueError(
+                    '--xbar_cell_bits cannot be combined with --%s: T * J '
+                    'accumulator sets per output do not fit the kernel, and '
+                    'W+ / W- columns per weight slice are a follow-up'
+                    % ('xbar_diff' if self.xbar_diff else 'xbar_dac_bits'))
+            for k in (1, 2, 3, 4):
+                q_w = getattr(a, 'q_w%d' % k)
+                if not 0 < q_w < 8:
+                    raise ValueError(
+                        '--xbar_cell_bits needs quantised weights on every '
+                        'layer, 0 < q_w < 8 (8-bit weights of a linear layer '
+                        'stay unquantised): --q_w%d is %d' % (k, q_w))
+                if -(-q_w // E) > 4:
+                    raise ValueError(
+                        '--xbar_cell_bits %d cuts --q_w%d %d into %d slices, '
+                        'at most 4 are built; the smallest --xbar_cell_bits '
+                        'that works is %d' % (E, k, q_w, -(-q_w // E),
+                                              -(-q_w // 4)))
         flags = self._introspective_flags()
         if flags:
             raise ValueError(
@@ -298,6 +346,28 @@ class Net(nn.Module):
         return dict(in_bits=q_a, dac_bits=self.xbar_dac_bits,
                     x_step=max((hi - lo) / (2.0 ** q_a - 1.0), 1e-6))
 
+    def _xbar_cell_args(self, layer_num, layer, dtype):
+        """w_bits / cell_bits / w_step / w_min of a layer under
+        --xbar_cell_bits: the code width is the layer's q_w, the grid that of
+        the range its weight quantiser has just quantised with. Decided from
+        the range's floats alone (no device read)."""
+        if self.xbar_cell_bits <= 0:
+            return {}
+        k = layer_num + 1
+        q_w = getattr(self.args, 'q_w%d' % k)
+        lo, hi = layer.quantize_weights.last_range
+        w_step = max((hi - lo) / (2.0 ** q_w - 1.0), 1e-6)
+        # one rounding to the dtype moves a grid weight by at most
+        # max|w| * u; the code is recovered while that stays below half a step
+        u = torch.finfo(dtype).eps / 2
+        if max(abs(lo), abs(hi)) * u >= w_step / 2:
+            raise ValueError(
+                '--xbar_cell_bits: the %d-bit weight codes of layer %d on the '
+                'range [%g, %g] (step %g) cannot be recovered from %s weights'
+                % (q_w, k, lo, hi, w_step, dtype))
+        return dict(w_bits=q_w, cell_bits=self.xbar_cell_bits, w_step=w_step,
+                    w_min=lo)
+
     def _xbar_layer(self, x, layer, current, merged_dac, i, layer_num,
                     is_conv):
         """The layer on tiled crossbars: per-tile noise when its current is
@@ -329,6 +399,7 @@ class Net(nn.Module):
                     power_denom = input_max
         telem = ops.XbarTelemetry() if want_telemetry else None
         serial = self._xbar_serial_args(layer_num)
+        serial.update(self._xbar_cell_args(layer_num, layer, wq.dtype))
         if is_conv:
             out = ops.xbar_noisy_conv2d(
                 x, wq, w_raw.detach(), bias, 1, 0, sigma_mode, factor,

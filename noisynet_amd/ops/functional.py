@@ -643,7 +643,15 @@ class XbarTelemetry(NoiseTelemetry):
     SLICE partial: the share is over the J * nblocks * M * K values v_bj and
     ``partial_absmax`` is the max |v_bj| -- the number to size the per-slice
     ``adc_max`` from, much smaller than the unsliced one. power is what the
-    unsliced op reports for on-grid inputs; nsr uses the shift-added noise."""
+    unsliced op reports for on-grid inputs; nsr uses the shift-added noise.
+
+    With bit-sliced weights (``cell_bits`` > 0, T slices) both figures are per
+    cell SLICE partial: the share is over the T * nblocks * M * K unipolar
+    column values v_bt (beyond the top code or below zero) and
+    ``partial_absmax`` is the max |v_bt|, the number to size the per-slice
+    ``adc_max`` from. power is computed from the current the offset-binary
+    cells draw (sum p_bt, not shift-weighted), which is higher than the
+    signed one-cell model's; nsr uses the shift-added noise."""
 
     __slots__ = ("adc_clip_share", "partial_absmax")
 
@@ -660,20 +668,28 @@ _XBAR_MODE = {None: 0, "abs": 1, "abs2": 2}
 def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
                   sigma_mode, factor, xbar_rows, adc_bits, adc_max,
                   want_telemetry, differential=False, in_bits=0, dac_bits=0,
-                  x_step=None):
+                  x_step=None, w_bits=0, cell_bits=0, w_step=None, w_min=None):
     """Shared forward of the two xbar Functions. Returns (y, tele) with tele a
     dict of 0-dim tensors (or None): sigma_abs, abs_noise, max_y, clipped,
     n_partials, partial_absmax -- sums over the whole call. ``differential``
     runs W+ / W- columns with unipolar ADCs (two partials per block);
-    ``dac_bits`` > 0 streams the input in J slices (J partials per block)."""
+    ``dac_bits`` > 0 streams the input in J slices (J partials per block);
+    ``cell_bits`` > 0 spreads the weight code over T columns with unipolar
+    ADCs (T partials per block)."""
     x = x2_or_x
     differential = bool(differential)
     adc = ref.xbar_adc_params(adc_bits, adc_max, x.device,
-                              unipolar=differential)
+                              unipolar=differential or bool(cell_bits))
     n_rows = wq[0].numel()
     nblocks = -(-n_rows // int(xbar_rows))
     dac, serial, slices = None, (), 1
-    if dac_bits:
+    cell = None
+    if cell_bits:
+        slices = -(-int(w_bits) // int(cell_bits))
+        cell = ref.xbar_cell_params(w_step, w_min, x.device)
+        serial = (int(w_bits), int(cell_bits), cell)
+        fwd_conv, fwd_linear = "xbar_cells_fwd_conv", "xbar_cells_fwd_linear"
+    elif dac_bits:
         slices = -(-int(in_bits) // int(dac_bits))
         dac = ref.xbar_dac_params(x_step, x.device)
         serial = (int(in_bits), int(dac_bits), dac)
@@ -692,7 +708,16 @@ def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
                   adc if adc is not None else empty_f) + serial + (
                   _next_seed(x.device), bool(want_telemetry))
         wr = w_raw if sigma_mode is not None else wq
-        if is_conv:
+        if cell_bits:       # the conductances are the digits: no w_raw
+            if is_conv:
+                y, t = getattr(ext(), fwd_conv)(
+                    _nhwc(x), _nhwc(wq), bias if bias is not None else empty,
+                    stride, padding, *common)
+            else:
+                y, t = getattr(ext(), fwd_linear)(
+                    x.contiguous(), wq.contiguous(),
+                    bias if bias is not None else empty, *common)
+        elif is_conv:
             y, t = getattr(ext(), fwd_conv)(
                 _nhwc(x), _nhwc(wq), _nhwc(wr),
                 bias if bias is not None else empty, stride, padding, *common)
@@ -718,12 +743,13 @@ def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
             xm = xd
         ym = ref.xbar_vmm(
             xm, ref.xbar_weight_rows(wq.detach()),
-            ref.xbar_weight_rows(w_raw.detach()) if sigma_mode is not None
-            else None,
+            ref.xbar_weight_rows(w_raw.detach())
+            if sigma_mode is not None and not cell_bits else None,
             bias.detach() if bias is not None else None, sigma_mode, factor,
             int(xbar_rows), adc_bits, adc, stats=tele,
             differential=differential, dac=dac, in_bits=int(in_bits),
-            dac_bits=int(dac_bits))
+            dac_bits=int(dac_bits), cell=cell, w_bits=int(w_bits),
+            cell_bits=int(cell_bits))
         if is_conv:
             N, K = x.shape[0], wq.shape[0]
             oh = (x.shape[2] + 2 * padding - R) // stride + 1
@@ -754,20 +780,23 @@ class _XbarNoisyConv(torch.autograd.Function):
     noise and the ADC: exactly the gradients of the unblocked conv with wq.
     A clipped STE would need per-block saturation masks and is not built.
     ``differential`` selects xbar_diff_fwd_kernel (W+ / W- columns, unipolar
-    ADCs), ``dac_bits`` > 0 xbar_serial_fwd_kernel (bit-serial inputs); the
+    ADCs), ``dac_bits`` > 0 xbar_serial_fwd_kernel (bit-serial inputs),
+    ``cell_bits`` > 0 xbar_cells_fwd_kernel (bit-sliced weights); the
     backward is the same."""
 
     @staticmethod
     def forward(ctx, x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
                 xbar_rows, adc_bits, adc_max, want_telemetry, telemetry_out,
                 current, power_denom, differential=False, in_bits=0,
-                dac_bits=0, x_step=None):
+                dac_bits=0, x_step=None, w_bits=0, cell_bits=0, w_step=None,
+                w_min=None):
         ctx.stride, ctx.padding = stride, padding
         ctx.has_bias = bias is not None
         y, tele = _xbar_forward(x, True, wq, w_raw, bias, stride, padding,
                                 sigma_mode, factor, xbar_rows, adc_bits,
                                 adc_max, want_telemetry, differential,
-                                in_bits, dac_bits, x_step)
+                                in_bits, dac_bits, x_step, w_bits, cell_bits,
+                                w_step, w_min)
         if want_telemetry and telemetry_out is not None:
             _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
                           power_denom)
@@ -784,7 +813,7 @@ class _XbarNoisyConv(torch.autograd.Function):
             gw = ConvWgrad.apply(g, x, ctx.stride, ctx.padding, wq.shape, None)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum(dim=(0, 2, 3))
-        return (gx, gw, None, gb) + (None,) * 15
+        return (gx, gw, None, gb) + (None,) * 19
 
 
 class _XbarNoisyLinear(torch.autograd.Function):
@@ -794,12 +823,13 @@ class _XbarNoisyLinear(torch.autograd.Function):
     def forward(ctx, x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
                 adc_bits, adc_max, want_telemetry, telemetry_out, current,
                 power_denom, differential=False, in_bits=0, dac_bits=0,
-                x_step=None):
+                x_step=None, w_bits=0, cell_bits=0, w_step=None, w_min=None):
         ctx.has_bias = bias is not None
         y, tele = _xbar_forward(x, False, wq, w_raw, bias, 1, 0, sigma_mode,
                                 factor, xbar_rows, adc_bits, adc_max,
                                 want_telemetry, differential, in_bits,
-                                dac_bits, x_step)
+                                dac_bits, x_step, w_bits, cell_bits, w_step,
+                                w_min)
         if want_telemetry and telemetry_out is not None:
             _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
                           power_denom)
@@ -816,14 +846,15 @@ class _XbarNoisyLinear(torch.autograd.Function):
             gw = LinearWgrad.apply(g, x)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum(dim=0)
-        return (gx, gw, None, gb) + (None,) * 13
+        return (gx, gw, None, gb) + (None,) * 17
 
 
 def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
                       xbar_rows, adc_bits, adc_max, current=0.0,
                       power_denom=1.0, want_telemetry=False,
                       telemetry_out=None, differential=False, in_bits=0,
-                      dac_bits=0, x_step=None):
+                      dac_bits=0, x_step=None, w_bits=0, cell_bits=0,
+                      w_step=None, w_min=None):
     """Noisy conv on tiled crossbars.
 
     The contraction index is the filter's memory order (r, s, c), c fastest;
@@ -886,12 +917,47 @@ def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
     The telemetry's ADC figures are per slice partial (J * nblocks per
     output). ``dac_bits`` = 0 is the op without slicing. Differential columns
     with bit-serial inputs are not built. The backward is unchanged.
+
+    ``cell_bits`` = E in 1..4 slices the WEIGHTS: a cell holds E bits, so the
+    ``w_bits`` = B bit (1..8) offset-binary code of a weight on the grid
+    w = ``w_min`` + code * ``w_step`` (the weight quantiser's grid; numbers or
+    1-element tensors) is spread over T = ceil(B / E) <= 4 columns, each with
+    its own current, noise draw and UNIPOLAR ADC conversion; the digital side
+    shift-adds the columns and adds the offset. Per block b and slice t, in
+    fp32,
+        code = clamp(rint((wq - w_min) * (1/w_step)), 0, 2^B - 1)
+        d_t  = (code >> t*E) & (2^E - 1)      cell conductance g_t = w_step*d_t
+        p_bt = w_step * sum x*d_t
+        s_bt = max(sum x*f(g_t), 0)           f = g (abs), g^2 + g (abs2)
+        v_bt = p_bt + eps_bt * sqrt(factor * s_bt)   own draw per (b, t)
+        q_bt = step * clamp(rint(v_bt * (1/step)), 0, Qu)
+        X_b  = sum x                          (digital, exact)
+    with Qu = 2^adc_bits - 1, step = adc_max / Qu, and
+    out = sum_b (sum_t 2^(tE) q_bt + w_min * X_b) + bias, rounded once. The
+    weights are recovered from ``wq`` as codes, so with noise and ADC off the
+    op would compute x @ W_grid^T with the exact grid weights, not with the
+    dtype-rounded ``wq``; ``w_raw`` is not used -- the noise comes from the
+    cells, whose conductances are the digits. ``factor`` stays that of the
+    unsliced layer, so the output noise variance is
+    factor * sum_b sum_t 4^(tE) s_bt. Offset-binary cells carry current even
+    for a zero weight (code -w_min/w_step), so noise and power are higher than
+    the signed one-cell model's. ``adc_max`` is the range [0, adc_max] of ONE
+    column conversion (read ``partial_absmax``); the telemetry's ADC figures
+    are per slice partial (T * nblocks per output) and ``power`` is computed
+    from the current the cells draw, sum p_bt, not shift-weighted. Not
+    combinable with ``differential`` or ``dac_bits``. ``cell_bits`` = 0 is the
+    op with one analog cell per weight. The backward is unchanged.
     """
     if isinstance(stride, (tuple, list)):
         stride = stride[0]
     if isinstance(padding, (tuple, list)):
         padding = padding[0]
-    if dac_bits:
+    cells = ()
+    if cell_bits:
+        ref.xbar_check_cell_args(w_bits, cell_bits, w_step, w_min, sigma_mode,
+                                 adc_bits, differential, dac_bits)
+        cells = (w_bits, cell_bits, w_step, w_min)
+    elif dac_bits:
         ref.xbar_check_serial_args(in_bits, dac_bits, x_step, x.dtype,
                                    sigma_mode, adc_bits, differential)
     ref.xbar_check_args(sigma_mode, xbar_rows, adc_bits, adc_max)
@@ -899,20 +965,28 @@ def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
                                 sigma_mode, factor, xbar_rows, adc_bits,
                                 adc_max, want_telemetry, telemetry_out,
                                 current, power_denom, bool(differential),
-                                in_bits, dac_bits, x_step)
+                                in_bits, dac_bits, x_step, *cells)
 
 
 def xbar_noisy_linear(x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
                       adc_bits, adc_max, current=0.0, power_denom=1.0,
                       want_telemetry=False, telemetry_out=None,
-                      differential=False, in_bits=0, dac_bits=0, x_step=None):
+                      differential=False, in_bits=0, dac_bits=0, x_step=None,
+                      w_bits=0, cell_bits=0, w_step=None, w_min=None):
     """Noisy linear layer on tiled crossbars: xbar_noisy_conv2d with the input
     index as the crossbar row. Same straight-through backward (the gradients
     of F.linear(x, wq, bias)); a clipped STE is out of scope.
     ``differential=True`` selects the W+ / W- columns with unipolar ADCs
     described there (meant for non-negative activations); ``dac_bits`` > 0
-    the bit-serial inputs described there (``in_bits``, ``x_step``)."""
-    if dac_bits:
+    the bit-serial inputs described there (``in_bits``, ``x_step``),
+    ``cell_bits`` > 0 the bit-sliced weights described there (``w_bits``,
+    ``w_step``, ``w_min``)."""
+    cells = ()
+    if cell_bits:
+        ref.xbar_check_cell_args(w_bits, cell_bits, w_step, w_min, sigma_mode,
+                                 adc_bits, differential, dac_bits)
+        cells = (w_bits, cell_bits, w_step, w_min)
+    elif dac_bits:
         ref.xbar_check_serial_args(in_bits, dac_bits, x_step, x.dtype,
                                    sigma_mode, adc_bits, differential)
     ref.xbar_check_args(sigma_mode, xbar_rows, adc_bits, adc_max)
@@ -920,7 +994,7 @@ def xbar_noisy_linear(x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
                                   xbar_rows, adc_bits, adc_max,
                                   want_telemetry, telemetry_out, current,
                                   power_denom, bool(differential), in_bits,
-                                  dac_bits, x_step)
+                                  dac_bits, x_step, *cells)
 
 
 # ---------------------------------------------------------------------------

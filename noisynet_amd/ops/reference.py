@@ -175,6 +175,52 @@ def xbar_dac_params(x_step, device):
     return torch.cat([xs, 1.0 / xs])
 
 
+def xbar_check_cell_args(w_bits, cell_bits, w_step, w_min, sigma_mode,
+                         adc_bits, differential=False, dac_bits=0):
+    """Argument rules of the bit-sliced weight mode (``cell_bits`` > 0);
+    returns the slice count T = ceil(w_bits / cell_bits)."""
+    if int(cell_bits) != cell_bits or not 1 <= cell_bits <= 4:
+        raise ValueError("cell_bits must be 0 (one analog cell per weight) or "
+                         "1..4, got %r" % (cell_bits,))
+    if differential or dac_bits:
+        raise ValueError(
+            "bit-sliced weights (cell_bits > 0) cannot be combined with "
+            "differential=True or dac_bits > 0: T * J accumulator sets per "
+            "output do not fit the kernel's registers, and W+ / W- columns "
+            "per weight slice are a follow-up")
+    if int(w_bits) != w_bits or not 1 <= w_bits <= 8:
+        raise ValueError("w_bits must be 1..8, got %r" % (w_bits,))
+    slices = -(-int(w_bits) // int(cell_bits))
+    if slices > 4:
+        raise ValueError(
+            "w_bits %d at cell_bits %d is %d slices, at most 4 are built; the "
+            "smallest cell_bits that works is %d"
+            % (w_bits, cell_bits, slices, -(-int(w_bits) // 4)))
+    if w_step is None or w_min is None:
+        raise ValueError("cell_bits > 0 needs w_step and w_min, the weight "
+                         "quantiser's grid w = w_min + code * w_step")
+    if not isinstance(w_step, torch.Tensor) and not float(w_step) > 0:
+        raise ValueError("w_step must be > 0, got %r" % (w_step,))
+    if adc_bits == 0 and sigma_mode is None:
+        raise ValueError("xbar op with neither noise (sigma_mode) nor an ADC "
+                         "(adc_bits): bit-sliced weights have nothing to act "
+                         "on")
+    return slices
+
+
+def xbar_cell_params(w_step, w_min, device):
+    """fp32 tensor [w_step, 1/w_step, w_min], each rounded once to fp32 (the
+    values the kernel computes with). ``w_step`` / ``w_min`` are numbers or
+    1-element tensors (w_step must then be positive; it is not read back)."""
+    def one(v):
+        if isinstance(v, torch.Tensor):
+            return v.detach().to(device=device, dtype=torch.float32).reshape(1)
+        # a fill, not a host-to-device copy: legal under graph capture
+        return torch.full((1,), float(v), dtype=torch.float32, device=device)
+    ws, wm = one(w_step), one(w_min)
+    return torch.cat([ws, 1.0 / ws, wm])
+
+
 def xbar_conv_rows(x, R, S, stride, padding):
     """im2col matrix [N*OH*OW, R*S*C] of an NCHW input with the contraction
     index in the filter's memory order (r, s, c), c fastest -- the crossbar
@@ -195,7 +241,7 @@ def xbar_weight_rows(w):
 
 def xbar_vmm(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows, adc_bits,
              adc, gen=None, stats=None, differential=False, dac=None,
-             in_bits=0, dac_bits=0):
+             in_bits=0, dac_bits=0, cell=None, w_bits=0, cell_bits=0):
     """Blocked analog VMM on row matrices: xm [M, n], wqm / wrm [K, n].
 
     Block b covers rows [b*xbar_rows, min((b+1)*xbar_rows, n)). Per block
@@ -210,7 +256,17 @@ def xbar_vmm(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows, adc_bits,
     partial_absmax (max |v_b|). Returns fp32 [M, K].
 
     ``differential`` runs every block on two columns (see _xbar_vmm_diff);
-    ``dac_bits`` > 0 streams the input in slices (see _xbar_vmm_serial)."""
+    ``dac_bits`` > 0 streams the input in slices (see _xbar_vmm_serial);
+    ``cell_bits`` > 0 spreads the weight code over columns (see
+    _xbar_vmm_cells)."""
+    if cell_bits:
+        if differential or dac_bits:
+            raise ValueError("bit-sliced weights (cell_bits > 0) cannot be "
+                             "combined with differential columns or "
+                             "bit-serial inputs")
+        return _xbar_vmm_cells(xm, wqm, bias, sigma_mode, factor, xbar_rows,
+                               adc_bits, adc, cell, w_bits, cell_bits, gen,
+                               stats)
     if dac_bits:
         if differential:
             raise ValueError("differential columns with bit-serial inputs "
@@ -433,6 +489,98 @@ def _xbar_vmm_serial(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows,
         stats.update(sigma_abs=sig_abs, abs_noise=noise_tot.abs().sum(),
                      max_y=clean.max(), clipped=clipped,
                      n_partials=J * nblk * M * K, partial_absmax=absmax)
+    return out
+
+
+def _xbar_vmm_cells(xm, wqm, bias, sigma_mode, factor, xbar_rows, adc_bits,
+                    adc, cell, w_bits, cell_bits, gen=None, stats=None):
+    """xbar_vmm with bit-sliced weights: a cell holds ``cell_bits`` = E bits,
+    so the ``w_bits`` = B bit offset-binary code of a weight on the grid
+    w = w_min + code * w_step (``cell`` = [w_step, 1/w_step, w_min] of
+    xbar_cell_params) is spread over T = ceil(B/E) columns, each with its own
+    current, noise draw and UNIPOLAR ADC conversion:
+        code = clamp(rint((wq - w_min) * (1/w_step)), 0, 2^B - 1)
+        d_t  = (code >> t*E) & (2^E - 1)                       t = 0..T-1
+        p_bt = w_step * (x_b @ d_t^T)
+        s_bt = max(p_bt, 0)                                    (abs)
+             = max(w_step^2 * (x_b @ (d_t^2)^T) + p_bt, 0)     (abs2)
+        v_bt = p_bt + eps_bt * sqrt(factor * s_bt)
+        q_bt = step * clamp(rint(v_bt * (1/step)), 0, Qu),  Qu = 2^adc_bits - 1
+        X_b  = sum of the block's inputs
+    and out = sum_b (sum_t 2^(tE) q_bt + w_min * X_b) + bias in fp32 (b
+    ascending, t ascending inside b, then the block's offset). The
+    conductances are the digits: w_raw is not used. ``stats``: sigma_abs =
+    sum p_bt (the current the cells draw, not shift-weighted), abs_noise uses
+    the shift-added noises, max_y the clean shift-added sum with the offset
+    and the bias, clipped counts the (b, t) partials with rint(v/step) > Qu or
+    < 0, n_partials = T * nblocks * M * K and partial_absmax = max |v_bt| --
+    the figure to size the per-slice, unipolar adc_max from."""
+    E, B = int(cell_bits), int(w_bits)
+    T = -(-B // E)
+    w_step, inv_w_step, w_min = cell[0], cell[1], cell[2]
+    w_step2 = w_step * w_step
+    code = torch.round((wqm.float() - w_min) * inv_w_step)
+    code = code.clamp(0, float(2 ** B - 1)).to(torch.int32)
+    xm = xm.float()
+    n = xm.shape[1]
+    M, K = xm.shape[0], wqm.shape[0]
+    out = torch.zeros(M, K, dtype=torch.float32, device=xm.device)
+    if sigma_mode is not None:
+        factor = torch.as_tensor(factor, dtype=torch.float32, device=xm.device)
+    if adc is not None:
+        step, inv_step = adc[0], adc[1]
+        qu = float(2 ** int(adc_bits) - 1)
+    if stats is not None:
+        clean = torch.zeros_like(out)
+        noise_tot = torch.zeros_like(out)
+        sig_abs = out.new_zeros(())
+        clipped = 0
+        absmax = out.new_zeros(())
+        nblk = 0
+    for k0 in range(0, n, xbar_rows):
+        k1 = min(k0 + xbar_rows, n)
+        xb = xm[:, k0:k1]
+        for t in range(T):
+            shift = float(2 ** (t * E))
+            dt = ((code[:, k0:k1] >> (t * E)) & (2 ** E - 1)).float()
+            p = w_step * (xb @ dt.t())
+            v = p
+            if sigma_mode is not None:
+                s = p
+                if sigma_mode == "abs2":
+                    s = w_step2 * (xb @ (dt * dt).t()) + p
+                s = s.clamp_min(0)
+                eps = torch.randn(p.shape, dtype=torch.float32,
+                                  device=p.device, generator=gen)
+                nb = eps * (factor * s).sqrt()
+                v = p + nb
+            if adc is not None:
+                c = torch.round(v * inv_step)
+                q = step * c.clamp(0, qu)
+            else:
+                q = v
+            out = out + shift * q
+            if stats is not None:
+                clean = clean + shift * p
+                absmax = torch.maximum(absmax, v.abs().max())
+                if sigma_mode is not None:
+                    noise_tot = noise_tot + shift * nb
+                    sig_abs = sig_abs + p.sum()
+                if adc is not None:
+                    clipped = clipped + ((c > qu) | (c < 0)).sum()
+        off = w_min * xb.sum(dim=1, keepdim=True)
+        out = out + off
+        if stats is not None:
+            clean = clean + off
+            nblk += 1
+    if bias is not None:
+        out = out + bias.float()
+    if stats is not None:
+        if bias is not None:
+            clean = clean + bias.float()
+        stats.update(sigma_abs=sig_abs, abs_noise=noise_tot.abs().sum(),
+                     max_y=clean.max(), clipped=clipped,
+                     n_partials=T * nblk * M * K, partial_absmax=absmax)
     return out
 
 

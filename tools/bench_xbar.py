@@ -26,6 +26,14 @@ and for xbar_rows in {64, 128, 256}:
                 bf16 matmuls, randn noise, round / clamp and the shift-add,
                 J x the matmuls of (c); the slice row matrices are built once,
                 outside the timed region
+  (f) cells     (a) with bit-sliced weights: w_bits 4, cell_bits 1 (T = 4
+                slices) and 2 (T = 2), the weights put on the 4-bit grid
+                beforehand; T noise draws and T unipolar ADC conversions per
+                block plus the digital offset w_min * sum x, still one kernel
+  (f') eager_cells  the eager bit-sliced composition: per block and slice two
+                bf16 matmuls (digits and their squares), randn noise, round /
+                clamp and the shift-add, per block the offset; the digit
+                matrices are built once, outside the timed region
 
 Device events around windows of at least --window seconds after a warm-up,
 the variants alternating over --rounds rounds in one process; the median
@@ -34,8 +42,8 @@ CPU fallback: a time is a GPU time or it is not reported.
 
 --resource-usage needs no GPU: it compiles csrc/conv_mfma.hip for gfx950 with
 -Rpass-analysis=kernel-resource-usage and prints VGPRs, LDS and scratch of
-every xbar_fwd_kernel, xbar_diff_fwd_kernel and xbar_serial_fwd_kernel
-instantiation.
+every xbar_fwd_kernel, xbar_diff_fwd_kernel, xbar_serial_fwd_kernel and
+xbar_cells_fwd_kernel instantiation.
 """
 
 import argparse
@@ -64,6 +72,11 @@ IN_BITS, X_STEP, DAC_BITS = 4, 1.0 / 15.0, (1, 2)
 # a slice partial is far smaller than a full-code one: +-3 would round nearly
 # all of them to 0 and make the agreement check empty
 SERIAL_ADC_MAX = 0.25
+# bit-sliced weights: the 4-bit grid over [-0.3, 0.3] (3 sigma of the weights)
+W_BITS, W_RANGE, CELL_BITS = 4, (-0.3, 0.3), (1, 2)
+W_STEP = (W_RANGE[1] - W_RANGE[0]) / (2 ** W_BITS - 1)
+# the range [0, adc_max] of one unipolar slice conversion
+CELL_ADC_MAX = 4.0
 
 
 def eager_blocked(xm, wq, fw, factor, xbar_rows, step, inv_step, qm,
@@ -135,6 +148,43 @@ def eager_serial(slices, wq, fw, factor, xbar_rows, step, inv_step, qm,
                 * (step * torch.round(v * inv_step).clamp(-qm, qm))
             out = q if out is None else out + q
     return out
+
+
+def eager_cells(xm, digits, squares, factor, xbar_rows, step, inv_step, qu,
+                w_step, w_min, cell_bits, fp32_matmul=False):
+    """The bit-sliced-weight model composed of stock torch ops: per block and
+    per slice a digit matmul, a squared-digit matmul, randn noise and a
+    unipolar round / clamp, then the shift-add; per block the offset
+    w_min * sum x; every partial through memory. ``digits`` / ``squares`` are
+    the matrices d_t / d_t^2, prepared once, outside the timed region."""
+    if fp32_matmul:
+        xm = xm.float()
+        digits = [d.float() for d in digits]
+        squares = [d.float() for d in squares]
+    n = xm.shape[1]
+    out = None
+    for k0 in range(0, n, xbar_rows):
+        k1 = min(k0 + xbar_rows, n)
+        xb = xm[:, k0:k1]
+        for t, (d, d2) in enumerate(zip(digits, squares)):
+            p = w_step * (xb @ d[:, k0:k1].t()).float()
+            s = (w_step * w_step * (xb @ d2[:, k0:k1].t()).float()
+                 + p).clamp_min(0)
+            v = p + torch.randn_like(p) * (factor * s).sqrt()
+            q = float(2 ** (t * cell_bits)) \
+                * (step * torch.round(v * inv_step).clamp(0, qu))
+            out = q if out is None else out + q
+        out = out + w_min * xb.float().sum(dim=1, keepdim=True)
+    return out
+
+
+def make_digits(wq_rows, w_step, w_min, w_bits, cell_bits):
+    cell = ref.xbar_cell_params(w_step, w_min, wq_rows.device)
+    code = torch.round((wq_rows.float() - cell[2]) * cell[1]) \
+        .clamp(0, 2 ** w_bits - 1).to(torch.int32)
+    return [((code >> (t * cell_bits)) & (2 ** cell_bits - 1))
+            .to(wq_rows.dtype).contiguous()
+            for t in range(-(-w_bits // cell_bits))]
 
 
 def make_slices(xm, x_step, in_bits, dac_bits):
@@ -270,6 +320,42 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
             variants['serial_d%d' % D] = run_serial
             variants['eager_serial_d%d' % D] = run_eager_serial
         del xm_all
+        # bit-sliced weights: wq on the grid, digit matrices per cell width
+        wg = ref.fake_quant_forward(wq.float(), W_BITS, W_RANGE[0],
+                                    W_RANGE[1], 0).to(dtype)
+        if conv:
+            wg = wg.contiguous(memory_format=torch.channels_last)
+        wg_rows = ref.xbar_weight_rows(wg).contiguous()
+        cell = ref.xbar_cell_params(W_STEP, W_RANGE[0], dev)
+        adc_c = ref.xbar_adc_params(ADC_BITS, CELL_ADC_MAX, dev, unipolar=True)
+        step_c, inv_step_c = adc_c[0], adc_c[1]
+        ckw = dict(w_bits=W_BITS, w_step=W_STEP, w_min=W_RANGE[0])
+        digits, squares, moved_cells = {}, {}, {}
+        for E in CELL_BITS:
+            digits[E] = make_digits(wg_rows, W_STEP, W_RANGE[0], W_BITS, E)
+            squares[E] = [(d * d).contiguous() for d in digits[E]]
+
+            def run_cells(E=E):
+                for _ in range(reps):
+                    if conv:
+                        ops.xbar_noisy_conv2d(x, wg, wg, None, 1, 0, MODE,
+                                              factor, rows, ADC_BITS,
+                                              CELL_ADC_MAX, cell_bits=E, **ckw)
+                    else:
+                        ops.xbar_noisy_linear(x, wg, wg, None, MODE, factor,
+                                              rows, ADC_BITS, CELL_ADC_MAX,
+                                              cell_bits=E, **ckw)
+                return reps
+
+            def run_eager_cells(E=E):
+                xm = ref.xbar_conv_rows(x, spec['w'][2], spec['w'][3], 1, 0) \
+                    if conv else x
+                eager_cells(xm, digits[E], squares[E], factor, rows, step_c,
+                            inv_step_c, qu, cell[0], cell[2], E)
+                return 1
+
+            variants['cells_e%d' % E] = run_cells
+            variants['eager_cells_e%d' % E] = run_eager_cells
         with torch.no_grad():
             # results must agree before speeds are compared: noise off, the
             # fused op against the eager composition on the same blocks
@@ -322,6 +408,27 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
                 diff = (a.float() - e.to(a.dtype).float()).abs()
                 moved_serial[D] = float(
                     (diff > 0.5 * float(step_s)).float().mean())
+            # and for the bit-sliced weights (unipolar slices plus the offset)
+            xm = ref.xbar_conv_rows(x, spec['w'][2], spec['w'][3], 1, 0) \
+                if conv else x
+            for E in CELL_BITS:
+                if conv:
+                    a = ops.xbar_noisy_conv2d(x, wg, wg, None, 1, 0, None, 0.0,
+                                              rows, ADC_BITS, CELL_ADC_MAX,
+                                              cell_bits=E, **ckw)
+                    a = a.permute(0, 2, 3, 1).reshape(-1, a.shape[1])
+                else:
+                    a = ops.xbar_noisy_linear(x, wg, wg, None, None, 0.0,
+                                              rows, ADC_BITS, CELL_ADC_MAX,
+                                              cell_bits=E, **ckw)
+                e = eager_cells(xm, digits[E], squares[E],
+                                torch.zeros(1, device=dev), rows, step_c,
+                                inv_step_c, qu, cell[0], cell[2], E,
+                                fp32_matmul=True)
+                diff = (a.float() - e.to(a.dtype).float()).abs()
+                moved_cells[E] = float(
+                    (diff > 0.5 * float(step_c)).float().mean())
+            del xm
             for fn in variants.values():    # warm-up: code objects, allocator
                 fn()
             torch.cuda.synchronize()
@@ -360,7 +467,16 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
             res['eager_serial_d%d_over_serial' % D] = round(eag / ser, 2)
             res['serial_d%d_noise_off_outputs_off_by_a_step_vs_eager' % D] = \
                 moved_serial[D]
-        del slices
+        res.update(w_bits=W_BITS, cell_adc_max=CELL_ADC_MAX)
+        for E in CELL_BITS:
+            cel, eag = sec['cells_e%d' % E], sec['eager_cells_e%d' % E]
+            res['cells_e%d_ms' % E] = round(cel * 1e3, 4)
+            res['eager_cells_e%d_ms' % E] = round(eag * 1e3, 4)
+            res['cells_e%d_over_xbar' % E] = round(cel / sec['xbar'], 3)
+            res['eager_cells_e%d_over_cells' % E] = round(eag / cel, 2)
+            res['cells_e%d_noise_off_outputs_off_by_a_step_vs_eager' % E] = \
+                moved_cells[E]
+        del slices, digits, squares
         print(json.dumps(res), flush=True)
         results.append(res)
     return results
@@ -394,7 +510,8 @@ def parse_resource_usage(text):
             cur = {'kernel': m.group(1)} \
                 if ('xbar_fwd_kernel' in m.group(1)
                     or 'xbar_diff_fwd_kernel' in m.group(1)
-                    or 'xbar_serial_fwd_kernel' in m.group(1)) else None
+                    or 'xbar_serial_fwd_kernel' in m.group(1)
+                    or 'xbar_cells_fwd_kernel' in m.group(1)) else None
             if cur is not None:
                 rows.append(cur)
             continue
@@ -412,8 +529,10 @@ def parse_resource_usage(text):
     # top of the static bytes reported above
     diff = [r for r in rows if 'xbar_diff_fwd_kernel' in r['kernel']]
     serial = [r for r in rows if 'xbar_serial_fwd_kernel' in r['kernel']]
+    cells = [r for r in rows if 'xbar_cells_fwd_kernel' in r['kernel']]
     summarise('xbar_fwd_kernel',
-              [r for r in rows if r not in diff and r not in serial], 256)
+              [r for r in rows if r not in diff and r not in serial
+               and r not in cells], 256)
     summarise('xbar_diff_fwd_kernel', diff, 384)
     # (J*64 + 3*64) rows; the mangled name carries T (DF16b / DF16_ / f), J,
     # SIGMA_MODE, ADC and TELEM as I<T>Li<J>ELi<mode>ELb<adc>ELb<telem>E
@@ -425,6 +544,15 @@ def parse_resource_usage(text):
                   and 'kernelIf' not in r['kernel']]
         summarise('xbar_serial_fwd_kernel J=%d, 16-bit, no telemetry' % J,
                   steady, 64 * J + 192)
+    # (64 + T*64) rows, twice the T*64 with abs2 (the tiles of squares)
+    for T in (1, 2, 3, 4):
+        of_t = [r for r in cells
+                if re.search(r'kernelI\w+?Li%dELi\dELb' % T, r['kernel'])]
+        summarise('xbar_cells_fwd_kernel T=%d' % T, of_t, 64 + 128 * T)
+        steady = [r for r in of_t if r['kernel'].split('ELb')[2][0] == '0'
+                  and 'kernelIf' not in r['kernel']]
+        summarise('xbar_cells_fwd_kernel T=%d, 16-bit, no telemetry' % T,
+                  steady, 64 + 128 * T)
     return rows
 
 
@@ -472,6 +600,10 @@ def main():
                 if not r['serial_d%d_ms' % D] < r['eager_serial_d%d_ms' % D]:
                     slower.append((name, r['xbar_rows'],
                                    'bit-serial dac_bits %d' % D))
+            for E in CELL_BITS:
+                if not r['cells_e%d_ms' % E] < r['eager_cells_e%d_ms' % E]:
+                    slower.append((name, r['xbar_rows'],
+                                   'bit-sliced cell_bits %d' % E))
     if slower:
         raise SystemExit('fused op not faster than the eager composition at '
                          '%s' % slower)
