@@ -211,6 +211,24 @@ std::vector<torch::Tensor> xbar_cells_fwd_linear(
     torch::Tensor adc, int64_t w_bits, int64_t cell_bits, torch::Tensor cell,
     int64_t seed, bool telem);
 
+// programmed cells: G[T, K, n] (digit units) written once per layer by
+// xbar_program_cells (device-to-device variation, stuck-at cells) and read by
+// the fused bit-sliced VMM in place of the ideal digits
+std::vector<torch::Tensor> xbar_prog_fwd_conv(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor cells, torch::Tensor bias,
+    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
+    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t w_bits,
+    int64_t cell_bits, torch::Tensor cell, int64_t seed, bool telem);
+std::vector<torch::Tensor> xbar_prog_fwd_linear(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor cells, torch::Tensor bias,
+    int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
+    int64_t adc_bits, torch::Tensor adc, int64_t w_bits, int64_t cell_bits,
+    torch::Tensor cell, int64_t seed, bool telem);
+torch::Tensor xbar_program_cells(torch::Tensor wq, int64_t w_bits,
+                                 int64_t cell_bits, torch::Tensor cell,
+                                 double sigma, double p_stuck_off,
+                                 double p_stuck_on, int64_t seed, bool fresh);
+
 std::string conv_fused_route(int64_t C, int64_t H, int64_t W, int64_t K,
                              int64_t R, int64_t S, int64_t stride, int64_t pad,
                              int64_t elem_size);
@@ -289,4 +307,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xbar_serial_fwd_linear", &xbar_serial_fwd_linear);
   m.def("xbar_cells_fwd_conv", &xbar_cells_fwd_conv);
   m.def("xbar_cells_fwd_linear", &xbar_cells_fwd_linear);
+  m.def("xbar_prog_fwd_conv", &xbar_prog_fwd_conv);
+  m.def("xbar_prog_fwd_linear", &xbar_prog_fwd_linear);
+  m.def("xbar_program_cells", &xbar_program_cells);
 }

@@ -4465,7 +4465,20 @@ void xbar_serial_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
 //        y with the offset and the bias, (unused, see sat_count), max |v_bt|;
 //        sat_count = number of (b, t) partials with rint(v_bt / step) > Qu
 //        or < 0
-template <typename T, int NSLICE, int SIGMA_MODE, bool ADC, bool TELEM>
+//
+// PROG ("programmed cells"): the conductances are DATA, not digits. ``cells``
+// is G[NSLICE][K][wpitch] in digit units, written once per layer by
+// xbar_program_cells_kernel (device-to-device variation, stuck-at cells):
+//   p_bt = w_step * sum x * G_t
+//   s_bt = max(p_bt, 0)                                                (abs)
+//        = max(w_step^2 * sum x * round_to_dtype(f32(G_t)^2) + p_bt, 0) (abs2)
+// and everything from v_bt on is the model above. The staging thread loads
+// its 8-span of each of the NSLICE slices of G (in flight under the MFMAs,
+// as the wq span is), stores them as the conductance tiles and, with abs2,
+// their squares (fp32, rounded once). wq is not read; spans past K or past
+// the contraction are zeros. G^2 != G, so ``fold_squares`` is never set.
+template <typename T, int NSLICE, int SIGMA_MODE, bool ADC, bool TELEM,
+          bool PROG>
 __global__ __launch_bounds__(kBlock)
 void xbar_cells_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
                            const float* __restrict__ bias,
@@ -4477,7 +4490,9 @@ void xbar_cells_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
                            const float* __restrict__ adc_p /* step, 1/step */,
                            float qu, uint64_t seed, float* __restrict__ telem,
                            unsigned long long* __restrict__ sat_count,
-                           const int64_t* __restrict__ seed_base) {
+                           const int64_t* __restrict__ seed_base,
+                           const T* __restrict__ cells /* PROG: G */,
+                           int64_t cell_stride /* K * wpitch */) {
   seed = graph_seed(seed_base, seed);
   const float factor = (SIGMA_MODE > 0) ? factor_p[0] : 0.0f;
   const float step = ADC ? adc_p[0] : 1.0f;
@@ -4539,10 +4554,37 @@ void xbar_cells_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
   int steps_left = steps_per_block;
   int b = 0;
   XbarRegs<T> rg;   // rg.w stays unused: the conductances are the digits
+  // PROG: the thread's span of every slice of G, in place of rg.q
+  alignas(16) T gq[PROG ? NSLICE : 1][8];
   xbar_load_x(rg.x, x, g, xr);
-  xbar_load_w<T, 0>(rg.q, rg.w, wq, wq, g.K, n0, 0, nrows, wpitch);
+  if (PROG) {
+#pragma unroll
+    for (int t = 0; t < NSLICE; ++t)
+      xbar_load_w<T, 0>(gq[PROG ? t : 0], rg.w, cells + t * cell_stride, cells,
+                        g.K, n0, 0, nrows, wpitch);
+  } else {
+    xbar_load_w<T, 0>(rg.q, rg.w, wq, wq, g.K, n0, 0, nrows, wpitch);
+  }
   for (int ck = 0; ck < nrows; ck += BK) {
-    {
+    if (PROG) {
+      // the conductance tiles as they are; squares in fp32, rounded once
+      int row = threadIdx.x >> 2;
+      int seg = threadIdx.x & 3;
+      xbar_put8<T>(a_lds, row, seg, rg.x);
+#pragma unroll
+      for (int t = 0; t < NSLICE; ++t) {
+        xbar_put8<T>(d_lds + t * BN * STR, row, seg, gq[PROG ? t : 0]);
+        if (SIGMA_MODE == 2) {
+          float d[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            float gv = to_f32(gq[PROG ? t : 0][e]);
+            d[e] = __fmul_rn(gv, gv);
+          }
+          Mma<T>::store8(e_lds + t * BN * STR, row, seg * 8, d);
+        }
+      }
+    } else {
       // the code, once; then one digit tile (and one of squares) per slice.
       // Rows past the contraction or past K stage the code of a zero weight:
       // their activations are zero / their outputs are never stored
@@ -4573,7 +4615,14 @@ void xbar_cells_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
     if (ck + BK < nrows) {  // next step's loads, in flight under the MFMAs
       xbar_row_advance(xr, g, BK);
       xbar_load_x(rg.x, x, g, xr);
-      xbar_load_w<T, 0>(rg.q, rg.w, wq, wq, g.K, n0, ck + BK, nrows, wpitch);
+      if (PROG) {
+#pragma unroll
+        for (int t = 0; t < NSLICE; ++t)
+          xbar_load_w<T, 0>(gq[PROG ? t : 0], rg.w, cells + t * cell_stride,
+                            cells, g.K, n0, ck + BK, nrows, wpitch);
+      } else {
+        xbar_load_w<T, 0>(rg.q, rg.w, wq, wq, g.K, n0, ck + BK, nrows, wpitch);
+      }
     }
 #pragma unroll
     for (int fm = 0; fm < 2; ++fm) {
@@ -4705,6 +4754,63 @@ void xbar_cells_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
       atomic_max_f32(&telem[4], fmaxf(fmaxf(redm[1][0], redm[1][1]),
                                       fmaxf(redm[1][2], redm[1][3])));
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Programming a layer's weight codes onto imperfect cells: one launch writes
+// G[NSLICE][K][pitch] (digit units, the dtype of wq) for the PROG path above.
+// For the weight matrix in crossbar-row order [K, n], slice t, column k, row i
+//   code   = clamp(rint((f32(wq) - w_min) * inv_w_step), 0, 2^B - 1)
+//   d_t    = (code >> tE) & (2^E - 1)
+//   (u, z) = ONE Philox4x32 draw, key = chip seed, counter = (t*K + k)*n + i:
+//            u = u01(word 0), z = Box-Muller on words 2, 3
+//   d'_t   = 0 if u < p_off (stuck at the high-resistance state),
+//            2^E - 1 else if u < p_off + p_on (stuck on), else d_t
+//   G_t    = round_to_dtype(max(d'_t * (1 + sigma * z), 0))
+// in fp32 with the one rounding. Multiplicative Gaussian variation clamped at
+// zero: an off cell stays off, a stuck-on cell varies like any other.
+// Log-normal variation and additive HRS leakage are not modelled. One thread
+// owns a (k, i) and walks the slices; columns n..pitch-1 are written as zeros.
+// ``fresh`` sends the seed through graph_seed, so a captured step programs a
+// new chip on every replay; a fixed chip keeps the seed as given.
+// ---------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kBlock)
+void xbar_program_cells_kernel(const T* __restrict__ wq, T* __restrict__ G,
+                               int K, int n, int pitch, int nslice,
+                               int w_bits, int cell_bits,
+                               const float* __restrict__ cell_p,
+                               float sigma, float p_off, float p_on,
+                               uint64_t seed, int fresh,
+                               const int64_t* __restrict__ seed_base) {
+  if (fresh) seed = graph_seed(seed_base, seed);
+  int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (idx >= (int64_t)K * pitch) return;
+  int k = (int)(idx / pitch);
+  int i = (int)(idx - (int64_t)k * pitch);
+  const int64_t slice = (int64_t)K * pitch;
+  if (i >= n) {
+    for (int t = 0; t < nslice; ++t) G[t * slice + idx] = from_f32<T>(0.0f);
+    return;
+  }
+  const float inv_w_step = cell_p[1];
+  const float w_min = cell_p[2];
+  const float code_max = (float)((1 << w_bits) - 1);
+  const int dmask = (1 << cell_bits) - 1;
+  const float p_any = __fadd_rn(p_off, p_on);
+  float c = rintf((to_f32(wq[(int64_t)k * n + i]) - w_min) * inv_w_step);
+  int code = (int)fminf(fmaxf(c, 0.0f), code_max);
+  for (int t = 0; t < nslice; ++t) {
+    Philox4 p = philox4x32(seed, (uint64_t)(((int64_t)t * K + k) * n + i));
+    float u = u01(p.x);
+    float z = sqrtf(-2.0f * __logf(u01_open(p.z)))
+        * __cosf(6.2831853071795864f * u01(p.w));
+    float d = (float)((code >> (t * cell_bits)) & dmask);
+    if (u < p_off) d = 0.0f;
+    else if (u < p_any) d = (float)dmask;
+    float v = __fmul_rn(d, __fadd_rn(1.0f, __fmul_rn(sigma, z)));
+    G[t * slice + idx] = from_f32<T>(fmaxf(v, 0.0f));
   }
 }
 
@@ -5002,7 +5108,8 @@ std::vector<torch::Tensor> xbar_cells_fwd_impl(
     ConvGeom g, torch::Tensor out, int64_t sigma_mode,
     const torch::Tensor& factor, int64_t xbar_rows, int64_t adc_bits,
     const torch::Tensor& adc, int64_t w_bits, int64_t cell_bits,
-    const torch::Tensor& cell, int64_t seed, bool telem, const char* who) {
+    const torch::Tensor& cell, int64_t seed, bool telem, const char* who,
+    const torch::Tensor* cells = nullptr /* programmed conductances G */) {
   check_xbar_args(sigma_mode, xbar_rows, adc_bits, adc, x, who);
   const int NS = check_xbar_cells_args(w_bits, cell_bits, cell, x, who);
   int nrows = g.R * g.S * g.C;
@@ -5011,11 +5118,43 @@ std::vector<torch::Tensor> xbar_cells_fwd_impl(
   TORCH_CHECK(wq2.scalar_type() == x.scalar_type(), who,
               ": x and the weights must share one dtype");
   int pitch = nrows;
-  if (x.element_size() == 2 && (nrows & 7) != 0) {
-    pitch = (nrows + 7) & ~7;
-    wq2 = at::constant_pad_nd(wq2, {0, pitch - nrows}, 0);
+  const bool prog = cells != nullptr;
+  const bool padded = x.element_size() == 2 && (nrows & 7) != 0;
+  if (padded) pitch = (nrows + 7) & ~7;
+  torch::Tensor gc;
+  if (prog) {
+    // G[T, K, n]: contiguous, or the view xbar_program_cells returns (rows
+    // padded with zeros to a pitch of 8 elements), which is read in place
+    const torch::Tensor& c = *cells;
+    TORCH_CHECK(c.dim() == 3 && c.size(0) == NS && c.size(1) == g.K &&
+                    c.size(2) == nrows,
+                who, ": cells must have the shape [", NS, ", ", g.K, ", ",
+                nrows, "] (slices, output columns, crossbar rows), got ",
+                c.sizes());
+    TORCH_CHECK(c.scalar_type() == x.scalar_type(), who,
+                ": cells must have the dtype of x");
+    TORCH_CHECK(c.device() == x.device(), who,
+                ": cells must be on the device of x");
+    // (the padding must be inside the view's storage: the kernel reads it)
+    const bool pitched =
+        padded && c.stride(2) == 1 && c.stride(1) == pitch &&
+        c.stride(0) == (int64_t)g.K * pitch &&
+        (c.storage_offset() + (int64_t)NS * g.K * pitch) * c.element_size() <=
+            (int64_t)c.storage().nbytes();
+    TORCH_CHECK(c.is_contiguous() || pitched, who,
+                ": cells must be contiguous (or the row-padded view that "
+                "xbar_program_cells returns)");
+    // the 16-bit spans are 16-byte vector loads
+    const bool aligned = ((uintptr_t)c.data_ptr() & 15) == 0;
+    gc = c;
+    if (padded && !(pitched && aligned))
+      gc = at::constant_pad_nd(c, {0, pitch - nrows}, 0).contiguous();
+    else if (!aligned)
+      gc = c.clone();
+  } else {
+    if (padded) wq2 = at::constant_pad_nd(wq2, {0, pitch - nrows}, 0);
+    wq2 = wq2.contiguous();
   }
-  wq2 = wq2.contiguous();
   bool has_bias = bias.numel() > 0;
   if (has_bias) TORCH_CHECK(bias.numel() == g.K, who, ": bias size mismatch");
   torch::Tensor bias_f;
@@ -5033,7 +5172,8 @@ std::vector<torch::Tensor> xbar_cells_fwd_impl(
   bool adc_on = adc_bits > 0;
   float qu = adc_on ? (float)((1 << adc_bits) - 1) : 0.0f;   // unipolar
   // one-bit digits are their own squares: abs2 runs on the abs instantiation
-  const int fold = (sigma_mode == 2 && cell_bits == 1) ? 1 : 0;
+  // (not on programmed cells: G^2 != G)
+  const int fold = (sigma_mode == 2 && cell_bits == 1 && !prog) ? 1 : 0;
   const int64_t kmode = fold ? 1 : sigma_mode;
   dim3 grid((g.K + BN - 1) / BN, (int)((g.M + BM - 1) / BM));
   NN_DISPATCH(x.scalar_type(), "xbar_cells_fwd", [&] {
@@ -5054,12 +5194,15 @@ std::vector<torch::Tensor> xbar_cells_fwd_impl(
     const float* f = factor_f.data_ptr<float>();
     const float* ap = adc_on ? adc.data_ptr<float>() : nullptr;
     const float* cp = cell.data_ptr<float>();
+    const T* gp = prog ? (const T*)gc.data_ptr() : nullptr;
+    const int64_t gstride = (int64_t)g.K * pitch;
     uint64_t sd = (uint64_t)seed;
-    auto launch = [&](auto ns, auto sm, auto ad, auto tl) {
+    auto launch_pg = [&](auto ns, auto sm, auto ad, auto tl, auto pg) {
       auto kfn = xbar_cells_fwd_kernel<T, decltype(ns)::value,
                                        decltype(sm)::value,
                                        decltype(ad)::value,
-                                       decltype(tl)::value>;
+                                       decltype(tl)::value,
+                                       decltype(pg)::value>;
       if (lds > 65536)
         TORCH_CHECK(hipFuncSetAttribute(
                         (const void*)kfn,
@@ -5069,9 +5212,13 @@ std::vector<torch::Tensor> xbar_cells_fwd_impl(
       hipLaunchKernelGGL(kfn, grid, dim3(kBlock), lds, stream, xp, wqp, bp,
                          op, g, pitch, (int)xbar_rows, (int)w_bits,
                          (int)cell_bits, fold, cp, f, ap, qu, sd, tp, sp,
-                         g_seed_base);
+                         g_seed_base, gp, gstride);
     };
     using TT = std::true_type; using FF = std::false_type;
+    auto launch = [&](auto ns, auto sm, auto ad, auto tl) {
+      if (prog) launch_pg(ns, sm, ad, tl, TT{});
+      else launch_pg(ns, sm, ad, tl, FF{});
+    };
     auto with_telem = [&](auto ns, auto sm, auto ad) {
       if (telem) launch(ns, sm, ad, TT{}); else launch(ns, sm, ad, FF{});
     };
@@ -5136,6 +5283,97 @@ std::vector<torch::Tensor> xbar_cells_fwd_linear(
   return xbar_cells_fwd_impl(x, wq, bias, g, out, sigma_mode, factor,
                              xbar_rows, adc_bits, adc, w_bits, cell_bits,
                              cell, seed, telem, who);
+}
+
+// the same on programmed cells: ``cells`` = G[T, K, n] of
+// xbar_program_cells (digit units, the dtype of x) stands in for the digits;
+// wq gives the geometry only
+std::vector<torch::Tensor> xbar_prog_fwd_conv(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor cells, torch::Tensor bias,
+    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
+    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t w_bits,
+    int64_t cell_bits, torch::Tensor cell, int64_t seed, bool telem) {
+  const char* who = "xbar_prog_fwd_conv";
+  check_cl(x, "xbar_prog_fwd_conv x");
+  check_cl(wq, "xbar_prog_fwd_conv wq");
+  TORCH_CHECK(wq.size(1) == x.size(1), who, ": channel mismatch");
+  auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
+                     (int)x.size(1), (int)wq.size(0), (int)wq.size(2),
+                     (int)wq.size(3), (int)stride, (int)pad);
+  TORCH_CHECK(g.OH > 0 && g.OW > 0, who, ": empty output");
+  auto out = torch::empty({g.N, g.K, g.OH, g.OW},
+                          x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  int64_t nrows = (int64_t)g.R * g.S * g.C;
+  auto wq2 = wq.permute({0, 2, 3, 1}).reshape({(int64_t)g.K, nrows});
+  return xbar_cells_fwd_impl(x, wq2, bias, g, out, sigma_mode, factor,
+                             xbar_rows, adc_bits, adc, w_bits, cell_bits,
+                             cell, seed, telem, who, &cells);
+}
+
+std::vector<torch::Tensor> xbar_prog_fwd_linear(
+    torch::Tensor x, torch::Tensor wq, torch::Tensor cells, torch::Tensor bias,
+    int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
+    int64_t adc_bits, torch::Tensor adc, int64_t w_bits, int64_t cell_bits,
+    torch::Tensor cell, int64_t seed, bool telem) {
+  const char* who = "xbar_prog_fwd_linear";
+  TORCH_CHECK(wq.dim() == 2 && wq.size(1) == x.size(1), who,
+              ": weight shape mismatch");
+  auto g = linear_geom(x, wq.size(0));
+  auto out = torch::empty({x.size(0), wq.size(0)}, x.options());
+  return xbar_cells_fwd_impl(x, wq, bias, g, out, sigma_mode, factor,
+                             xbar_rows, adc_bits, adc, w_bits, cell_bits,
+                             cell, seed, telem, who, &cells);
+}
+
+// program a layer's weight codes onto imperfect cells (see
+// xbar_program_cells_kernel): wq is a channels-last conv filter [K, C, R, S]
+// (rows in the (r, s, c) order of xbar_cells_fwd_conv) or a linear weight
+// [K, n]. Returns G[T, K, n]; for the 16-bit dtypes the rows sit at a pitch
+// padded to 8 elements and the result is that view.
+torch::Tensor xbar_program_cells(torch::Tensor wq, int64_t w_bits,
+                                 int64_t cell_bits, torch::Tensor cell,
+                                 double sigma, double p_stuck_off,
+                                 double p_stuck_on, int64_t seed, bool fresh) {
+  const char* who = "xbar_program_cells";
+  TORCH_CHECK(wq.is_cuda(), who, ": wq must be a GPU tensor");
+  const int NS = check_xbar_cells_args(w_bits, cell_bits, cell, wq, who);
+  TORCH_CHECK(sigma >= 0.0, who, ": sigma must be >= 0, got ", sigma);
+  TORCH_CHECK(p_stuck_off >= 0.0, who, ": p_stuck_off must be >= 0, got ",
+              p_stuck_off);
+  TORCH_CHECK(p_stuck_on >= 0.0, who, ": p_stuck_on must be >= 0, got ",
+              p_stuck_on);
+  TORCH_CHECK(p_stuck_off + p_stuck_on <= 1.0, who,
+              ": p_stuck_off + p_stuck_on must be <= 1, got ",
+              p_stuck_off + p_stuck_on);
+  TORCH_CHECK(wq.dim() == 2 || wq.dim() == 4, who,
+              ": wq must be a [K, n] or a [K, C, R, S] tensor");
+  torch::Tensor wq2;
+  if (wq.dim() == 4) {
+    check_cl(wq, "xbar_program_cells wq");
+    wq2 = wq.permute({0, 2, 3, 1}).reshape({wq.size(0), -1}).contiguous();
+  } else {
+    wq2 = wq.contiguous();
+  }
+  const int64_t K = wq2.size(0), n = wq2.size(1);
+  TORCH_CHECK(K > 0 && n > 0 && (int64_t)NS * K * (n + 7) < (1ll << 31), who,
+              ": wq is empty or too large");
+  int64_t pitch = n;
+  if (wq2.element_size() == 2 && (n & 7) != 0) pitch = (n + 7) & ~(int64_t)7;
+  auto G = torch::empty({(int64_t)NS, K, pitch}, wq2.options());
+  const int64_t total = K * pitch;
+  NN_DISPATCH(wq2.scalar_type(), "xbar_program_cells", [&] {
+    using T = typename DevT<scalar_t>::type;
+    auto stream = c10::hip::getCurrentHIPStream();
+    hipLaunchKernelGGL(xbar_program_cells_kernel<T>,
+                       dim3((unsigned)((total + kBlock - 1) / kBlock)),
+                       dim3(kBlock), 0, stream, (const T*)wq2.data_ptr(),
+                       (T*)G.data_ptr(), (int)K, (int)n, (int)pitch, NS,
+                       (int)w_bits, (int)cell_bits, cell.data_ptr<float>(),
+                       (float)sigma, (float)p_stuck_off, (float)p_stuck_on,
+                       (uint64_t)seed, fresh ? 1 : 0, g_seed_base);
+  });
+  HIP_CHECK_LAST();
+  return pitch == n ? G : G.narrow(2, 0, n);
 }
 
 // bit-serial inputs (in_bits-bit codes on the grid x_step, dac_bits per

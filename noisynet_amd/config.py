@@ -134,7 +134,58 @@ def build_noisynet_parser():
                              'slice (0 = one analog cell per weight; needs '
                              '--xbar_rows and 0 < q_w < 8 on every layer, at '
                              'most 4 slices)')
+    # programmed cells: the bit-sliced arrays hold imperfect conductances
+    parser.add_argument('--xbar_cell_var', type=float, default=0.0, metavar='',
+                        help='device-to-device conductance variation of the '
+                             'bit-sliced cells: sigma of the multiplicative '
+                             'Gaussian 1 + sigma*z on every cell, clamped at '
+                             'zero (needs --xbar_cell_bits)')
+    parser.add_argument('--xbar_cell_stuck_off', type=float, default=0.0,
+                        metavar='',
+                        help='share of cells stuck at the high-resistance '
+                             'state, digit 0 (needs --xbar_cell_bits)')
+    parser.add_argument('--xbar_cell_stuck_on', type=float, default=0.0,
+                        metavar='',
+                        help='share of cells stuck on, at the top level '
+                             '2^bits - 1 of a cell (needs --xbar_cell_bits)')
+    parser.add_argument('--xbar_cell_seed', type=int, default=-1, metavar='',
+                        help='chip seed of the programmed cells: -1 draws a '
+                             'fresh chip whenever cells are programmed, S >= 0 '
+                             'is one fixed chip (layer k uses seed 4*S + k)')
     return parser
+
+
+def xbar_cell_model(args):
+    """(sigma, p_stuck_off, p_stuck_on, seed) of the programmed-cell model
+    after checking the four --xbar_cell_* flags, or None when all three rates
+    are 0 (ideal cells: the bit-sliced op runs on the digits)."""
+    sigma = getattr(args, 'xbar_cell_var', 0.0) or 0.0
+    p_off = getattr(args, 'xbar_cell_stuck_off', 0.0) or 0.0
+    p_on = getattr(args, 'xbar_cell_stuck_on', 0.0) or 0.0
+    seed = getattr(args, 'xbar_cell_seed', -1)
+    seed = -1 if seed is None else int(seed)
+    for flag, v in (('xbar_cell_var', sigma), ('xbar_cell_stuck_off', p_off),
+                    ('xbar_cell_stuck_on', p_on)):
+        if v < 0:
+            raise ValueError('--%s must be >= 0, got %r' % (flag, v))
+    if p_off + p_on > 1:
+        raise ValueError('--xbar_cell_stuck_off + --xbar_cell_stuck_on must '
+                         'be <= 1, got %r' % (p_off + p_on,))
+    if seed < -1:
+        raise ValueError('--xbar_cell_seed must be -1 (a fresh chip per '
+                         'programming) or >= 0, got %d' % seed)
+    if not (getattr(args, 'xbar_cell_bits', 0) or 0) > 0:
+        for flag, v in (('xbar_cell_var', sigma),
+                        ('xbar_cell_stuck_off', p_off),
+                        ('xbar_cell_stuck_on', p_on)):
+            if v > 0:
+                raise ValueError(
+                    '--%s needs --xbar_cell_bits > 0: conductance variation '
+                    'and stuck cells are a property of the bit-sliced cells'
+                    % flag)
+    if sigma == 0 and p_off == 0 and p_on == 0:
+        return None
+    return float(sigma), float(p_off), float(p_on), seed
 
 
 def broadcast_per_layer(args):

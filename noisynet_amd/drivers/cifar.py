@@ -26,7 +26,8 @@ from .. import data as data_mod
 from .. import ops
 from .. import optim as native_optim
 from .. import utils
-from ..config import broadcast_per_layer, build_noisynet_parser, var_list_for
+from ..config import (broadcast_per_layer, build_noisynet_parser,
+                      var_list_for, xbar_cell_model)
 from ..harness import merge_batchnorm, test_distortion
 from ..models.noisynet import Net
 from ..quant import QuantMeasure, finish_calibration, start_calibration
@@ -354,9 +355,20 @@ def print_xbar_stats(model, args):
     (J = ceil(q_a / D) conversions per tile and output), so the printed max is
     the figure for the per-slice --adc_max. With --xbar_cell_bits E they are
     per cell slice partial (T = ceil(q_w / E) unipolar conversions per tile
-    and output); the printed max is again the per-slice --adc_max figure."""
+    and output); the printed max is again the per-slice --adc_max figure.
+    With --xbar_cell_var / --xbar_cell_stuck_off / --xbar_cell_stuck_on the
+    cell model is named first: sigma_G, the stuck rates and the chip seed."""
     def mean(v):
         return float(np.mean(v)) if len(v) else float('nan')
+
+    cell_model = xbar_cell_model(args)
+    if cell_model is not None:
+        sigma, p_off, p_on, seed = cell_model
+        print('\txbar programmed cells: σ_G {:g}, stuck off {:g}, stuck on '
+              '{:g}, chip seed {}'.format(
+                  sigma, p_off, p_on,
+                  '{:d} (layer k uses {:d} + k)'.format(seed, 4 * seed)
+                  if seed >= 0 else 'fresh per programming'))
 
     diff = getattr(args, 'xbar_diff', False)
     dac_bits = getattr(args, 'xbar_dac_bits', 0) or 0

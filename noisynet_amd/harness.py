@@ -202,6 +202,73 @@ def test_distortion(model, args, val_loader=None, mode='weights', vars=None,
     return float(np.mean(acc_d, dtype=np.float64)) if acc_d else 0.0
 
 
+def test_cell_faults(model, args, val_loader, sigmas, stuck_rates, sims):
+    """Accuracy under programmed-cell non-idealities of the bit-sliced
+    crossbars (--xbar_cell_bits): every point of the grid ``sigmas`` x
+    ``stuck_rates`` is evaluated on ``sims`` chips, chip seeds 0..sims-1
+    (--xbar_cell_seed, so a seed names the same chip at every grid point).
+
+    ``sigmas`` are values of --xbar_cell_var; an entry of ``stuck_rates`` is a
+    pair (p_stuck_off, p_stuck_on) or one number, the stuck-off rate alone.
+    Unlike distort_weights / _stuck_at, which edit whole weights, the faults
+    act on the cells: a stuck MSB cell enters the output times 2^((T-1)E).
+
+    Returns a list with one dict per grid point, sigmas outermost:
+    ``sigma``, ``p_stuck_off``, ``p_stuck_on``, ``accs`` (one accuracy in
+    percent per chip), ``mean``, ``min``, ``max``. The model's weights are
+    not touched; the four --xbar_cell_* flags and the model's train / eval
+    mode are restored afterwards, also when an evaluation raises."""
+    flags = ('xbar_cell_var', 'xbar_cell_stuck_off', 'xbar_cell_stuck_on',
+             'xbar_cell_seed')
+    missing = object()
+    saved = {f: getattr(args, f, missing) for f in flags}
+    if not (getattr(args, 'xbar_cell_bits', 0) or 0) > 0:
+        raise ValueError('test_cell_faults needs --xbar_cell_bits > 0: the '
+                         'faults are a property of the bit-sliced cells')
+    was_training = model.training
+    results = []
+    try:
+        for sigma in sigmas:
+            for rate in stuck_rates:
+                p_off, p_on = rate if isinstance(rate, (tuple, list)) \
+                    else (rate, 0.0)
+                accs = []
+                for chip in range(int(sims)):
+                    args.xbar_cell_var = float(sigma)
+                    args.xbar_cell_stuck_off = float(p_off)
+                    args.xbar_cell_stuck_on = float(p_on)
+                    args.xbar_cell_seed = chip
+                    model.eval()       # drops the cells of the last chip
+                    te_accs = []
+                    with torch.no_grad():
+                        for input, label in _iter_val(val_loader, args):
+                            pred = model(input).data.max(1)[1]
+                            te_accs.append(
+                                pred.eq(label.data).float().mean().item()
+                                * 100.0)
+                    accs.append(float(np.mean(te_accs, dtype=np.float64)))
+                point = dict(sigma=float(sigma), p_stuck_off=float(p_off),
+                             p_stuck_on=float(p_on), accs=accs,
+                             mean=float(np.mean(accs, dtype=np.float64)),
+                             min=float(min(accs)), max=float(max(accs)))
+                results.append(point)
+                print('cell var {:>5.3f} stuck off {:>6.4f} on {:>6.4f}: {}  '
+                      'mean {:>5.2f} min {:>5.2f} max {:>5.2f}'.format(
+                          point['sigma'], point['p_stuck_off'],
+                          point['p_stuck_on'],
+                          [float('{:.2f}'.format(v)) for v in accs],
+                          point['mean'], point['min'], point['max']))
+    finally:
+        for f, v in saved.items():
+            if v is missing:
+                if hasattr(args, f):
+                    delattr(args, f)
+            else:
+                setattr(args, f, v)
+        model.train(was_training)
+    return results
+
+
 def merge_batchnorm(model, args):
     """Fold BN gamma/sqrt(var) into the preceding conv/linear weights in
     place (main.py:540-654). The bias term is then added at forward time

@@ -81,12 +81,41 @@ weights unquantised) and a range whose codes the dtype carries:
 max(|lo|, |hi|) * u_dtype < w_step / 2. Not combinable with --xbar_diff,
 --xbar_dac_bits or the introspective flags. With --xbar_cell_bits 0 nothing
 changes.
+
+Programmed cells (--xbar_cell_var sigma, --xbar_cell_stuck_off p,
+--xbar_cell_stuck_on p, --xbar_cell_seed S; with --xbar_cell_bits): the cells
+of the bit-sliced arrays hold imperfect conductances. Each crossbar layer
+programs its weight codes once (ops.xbar_program_cells, one HIP launch) into
+G[T, K, n] and the fused op reads G in place of the ideal digits
+(ops.xbar_noisy_*(..., cells=G)). Per cell, one (u, z) Philox draw keyed by
+the chip seed, counter (t*K + k)*n + i:
+    d'_t = 0 if u < p_off (stuck at the high-resistance state),
+           2^E - 1 else if u < p_off + p_on (stuck on), else d_t
+    G_t  = round_to_dtype(max(d'_t * (1 + sigma * z), 0))      (digit units)
+    p_bt = w_step * sum x * G_t
+    s_bt = max(p_bt, 0) (abs),  max(w_step^2 * sum x * G_t^2 + p_bt, 0) (abs2)
+and v_bt, the ADC, the shift-add and the exact digital offset w_min * sum x
+are those of the bit-sliced model. The variation is multiplicative and
+Gaussian, clamped at zero (an off cell stays off; a stuck-on cell varies like
+any other); log-normal variation and additive HRS leakage are not modelled. A
+fault in the MSB slice enters the output times 2^((T-1)E), which editing the
+weights cannot express. Gradients stay those of the plain layer on wq.
+Schedule: in training mode a layer programs its cells on every forward (the
+weights change); in eval mode once per weight version -- the cache is keyed on
+the weight parameter's ``_version`` / ``data_ptr`` (the effective weight is a
+fresh tensor per forward, derived from it), the quantiser's range, the dtype
+and the cell arguments, and is dropped on ``train()`` / ``eval()``. So one
+evaluation sees one chip. --xbar_cell_seed -1 (default) draws a fresh chip at
+every programming, so repeated evaluations see different chips; S >= 0 is one
+fixed chip, layer k (0..3) using seed 4*S + k. With all three rates 0 nothing
+changes: no cell is programmed and the op runs on the digits.
 """
 
 import torch
 from torch import nn
 
 from .. import ops
+from ..config import xbar_cell_model
 from ..hardware_model import NoisyConv2d, NoisyLinear, add_noise_calculate_power
 from ..quant import QuantMeasure
 
@@ -172,8 +201,15 @@ class Net(nn.Module):
             raise ValueError('--xbar_cell_bits needs --xbar_rows > 0: '
                              'bit-sliced weights are a mode of the tiled '
                              'crossbars')
-        if self.xbar_rows > 0:
+        self._cells_cache = {}
+        xbar_cell_model(args)     # the --xbar_cell_* flags, with or without
+        if self.xbar_rows > 0:    # --xbar_rows
             self._check_xbar_args()
+
+    def train(self, mode=True):
+        # programmed cells are cached in eval mode only, for one evaluation
+        self._cells_cache = {}
+        return super().train(mode)
 
     # ------------------------------------------------------------------
     _INTROSPECTIVE_BOOLS = ('plot', 'write', 'merge_bn', 'distort_act',
@@ -250,6 +286,7 @@ class Net(nn.Module):
                         'at most 4 are built; the smallest --xbar_cell_bits '
                         'that works is %d' % (E, k, q_w, -(-q_w // E),
                                               -(-q_w // 4)))
+        xbar_cell_model(a)
         flags = self._introspective_flags()
         if flags:
             raise ValueError(
@@ -368,6 +405,27 @@ class Net(nn.Module):
         return dict(w_bits=q_w, cell_bits=self.xbar_cell_bits, w_step=w_step,
                     w_min=lo)
 
+    def _xbar_cells(self, layer_num, layer, wq, cell_args):
+        """The layer's programmed conductances G under --xbar_cell_var /
+        --xbar_cell_stuck_*, or None for ideal cells. Training programs on
+        every forward; eval once per weight version (see module docstring)."""
+        model = xbar_cell_model(self.args)
+        if model is None or not cell_args:
+            return None
+        sigma, p_off, p_on, seed = model
+        chip = None if seed < 0 else 4 * seed + layer_num
+        kw = dict(sigma=sigma, p_stuck_off=p_off, p_stuck_on=p_on, seed=chip)
+        if self.training:
+            return ops.xbar_program_cells(wq, **cell_args, **kw)
+        w = layer.weight
+        key = (w._version, w.data_ptr(), wq.dtype, wq.device,
+               tuple(sorted(cell_args.items())), sigma, p_off, p_on, seed)
+        hit = self._cells_cache.get(layer_num)
+        if hit is None or hit[0] != key:
+            hit = (key, ops.xbar_program_cells(wq, **cell_args, **kw))
+            self._cells_cache[layer_num] = hit
+        return hit[1]
+
     def _xbar_layer(self, x, layer, current, merged_dac, i, layer_num,
                     is_conv):
         """The layer on tiled crossbars: per-tile noise when its current is
@@ -399,7 +457,11 @@ class Net(nn.Module):
                     power_denom = input_max
         telem = ops.XbarTelemetry() if want_telemetry else None
         serial = self._xbar_serial_args(layer_num)
-        serial.update(self._xbar_cell_args(layer_num, layer, wq.dtype))
+        cell_args = self._xbar_cell_args(layer_num, layer, wq.dtype)
+        serial.update(cell_args)
+        cells = self._xbar_cells(layer_num, layer, wq, cell_args)
+        if cells is not None:
+            serial['cells'] = cells
         if is_conv:
             out = ops.xbar_noisy_conv2d(
                 x, wq, w_raw.detach(), bias, 1, 0, sigma_mode, factor,

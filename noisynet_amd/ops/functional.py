@@ -665,17 +665,81 @@ class XbarTelemetry(NoiseTelemetry):
 _XBAR_MODE = {None: 0, "abs": 1, "abs2": 2}
 
 
+def _check_cells(cells, wq, w_bits, cell_bits):
+    slices = -(-int(w_bits) // int(cell_bits))
+    want = (slices, wq.shape[0], wq[0].numel())
+    if not isinstance(cells, torch.Tensor) or tuple(cells.shape) != want:
+        raise ValueError(
+            "cells must be the tensor G of xbar_program_cells with the shape "
+            "%r (slices, output columns, crossbar rows), got %r"
+            % (want, getattr(cells, "shape", cells)))
+
+
+def xbar_program_cells(wq, w_bits, cell_bits, w_step, w_min, sigma=0.0,
+                       p_stuck_off=0.0, p_stuck_on=0.0, seed=None):
+    """Program a layer's weight codes onto imperfect cells, once: returns the
+    conductances G[T, K, n] (digit units, the dtype of ``wq``) that
+    xbar_noisy_conv2d / xbar_noisy_linear read through ``cells=``.
+
+    ``wq`` is a conv filter [K, C, R, S] or a linear weight [K, n] on the
+    grid w = ``w_min`` + code * ``w_step`` (``w_bits`` = B bits), n = R*S*C in
+    the crossbar-row order (r, s, c), c fastest; T = ceil(B / E) slices of
+    ``cell_bits`` = E bit cells. For slice t, output column k and row i
+        code   = clamp(rint((f32(wq) - w_min) * (1/w_step)), 0, 2^B - 1)
+        d_t    = (code >> t*E) & (2^E - 1)
+        (u, z) = one Philox4x32 draw, key = chip seed,
+                 counter = (t*K + k)*n + i; u uniform on [0, 1) from word 0,
+                 z ~ N(0, 1) by Box-Muller on words 2 and 3
+        d'_t   = 0         if u < p_stuck_off   (stuck at the high-resistance
+                                                 state)
+               = 2^E - 1   else if u < p_stuck_off + p_stuck_on  (stuck on:
+                                                 the top level of the cell)
+               = d_t       otherwise
+        G_t    = round_to_dtype(max(d'_t * (1 + sigma * z), 0))
+    in fp32 with the one rounding. The variation is multiplicative and
+    Gaussian, clamped at zero: an off cell stays off, and a stuck-on cell is
+    still an analog device and varies like any other. Log-normal variation
+    and additive HRS leakage are not modelled.
+
+    ``seed`` None draws a fresh chip: the next seed of the global stream,
+    sent through the graph seed so that a captured step programs a new chip
+    on every replay. An int is one fixed chip, in eager mode and under
+    capture alike. One HIP launch on the GPU (for the 16-bit dtypes the rows
+    of the result sit at a pitch padded to 8 elements; the [T, K, n] tensor
+    returned is that view and the fused op reads it in place); CPU tensors
+    use the reference twin, which draws the same distribution from a
+    torch.Generator."""
+    ref.xbar_check_cell_args(w_bits, cell_bits, w_step, w_min, "abs", 0)
+    ref.xbar_check_program_args(sigma, p_stuck_off, p_stuck_on)
+    wq = wq.detach()
+    cell = ref.xbar_cell_params(w_step, w_min, wq.device)
+    if use_native(wq):
+        fresh = seed is None
+        s = _next_seed(wq.device) if fresh else int(seed)
+        w = _nhwc(wq) if wq.dim() == 4 else wq.contiguous()
+        return ext().xbar_program_cells(w, int(w_bits), int(cell_bits), cell,
+                                        float(sigma), float(p_stuck_off),
+                                        float(p_stuck_on), s, fresh)
+    gen = None
+    if seed is not None:
+        gen = torch.Generator(device=wq.device).manual_seed(int(seed))
+    return ref.xbar_program_cells(wq, w_bits, cell_bits, cell, sigma,
+                                  p_stuck_off, p_stuck_on, gen)
+
+
 def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
                   sigma_mode, factor, xbar_rows, adc_bits, adc_max,
                   want_telemetry, differential=False, in_bits=0, dac_bits=0,
-                  x_step=None, w_bits=0, cell_bits=0, w_step=None, w_min=None):
+                  x_step=None, w_bits=0, cell_bits=0, w_step=None, w_min=None,
+                  cells=None):
     """Shared forward of the two xbar Functions. Returns (y, tele) with tele a
     dict of 0-dim tensors (or None): sigma_abs, abs_noise, max_y, clipped,
     n_partials, partial_absmax -- sums over the whole call. ``differential``
     runs W+ / W- columns with unipolar ADCs (two partials per block);
     ``dac_bits`` > 0 streams the input in J slices (J partials per block);
     ``cell_bits`` > 0 spreads the weight code over T columns with unipolar
-    ADCs (T partials per block)."""
+    ADCs (T partials per block); ``cells`` then reads the programmed
+    conductances G[T, K, n] in place of the digits."""
     x = x2_or_x
     differential = bool(differential)
     adc = ref.xbar_adc_params(adc_bits, adc_max, x.device,
@@ -689,6 +753,8 @@ def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
         cell = ref.xbar_cell_params(w_step, w_min, x.device)
         serial = (int(w_bits), int(cell_bits), cell)
         fwd_conv, fwd_linear = "xbar_cells_fwd_conv", "xbar_cells_fwd_linear"
+        if cells is not None:
+            fwd_conv, fwd_linear = "xbar_prog_fwd_conv", "xbar_prog_fwd_linear"
     elif dac_bits:
         slices = -(-int(in_bits) // int(dac_bits))
         dac = ref.xbar_dac_params(x_step, x.device)
@@ -709,13 +775,15 @@ def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
                   _next_seed(x.device), bool(want_telemetry))
         wr = w_raw if sigma_mode is not None else wq
         if cell_bits:       # the conductances are the digits: no w_raw
+            prog = () if cells is None else (cells.detach(),)
             if is_conv:
                 y, t = getattr(ext(), fwd_conv)(
-                    _nhwc(x), _nhwc(wq), bias if bias is not None else empty,
+                    _nhwc(x), _nhwc(wq), *prog,
+                    bias if bias is not None else empty,
                     stride, padding, *common)
             else:
                 y, t = getattr(ext(), fwd_linear)(
-                    x.contiguous(), wq.contiguous(),
+                    x.contiguous(), wq.contiguous(), *prog,
                     bias if bias is not None else empty, *common)
         elif is_conv:
             y, t = getattr(ext(), fwd_conv)(
@@ -749,7 +817,8 @@ def _xbar_forward(x2_or_x, is_conv, wq, w_raw, bias, stride, padding,
             int(xbar_rows), adc_bits, adc, stats=tele,
             differential=differential, dac=dac, in_bits=int(in_bits),
             dac_bits=int(dac_bits), cell=cell, w_bits=int(w_bits),
-            cell_bits=int(cell_bits))
+            cell_bits=int(cell_bits),
+            **({} if cells is None else dict(cells=cells.detach())))
         if is_conv:
             N, K = x.shape[0], wq.shape[0]
             oh = (x.shape[2] + 2 * padding - R) // stride + 1
@@ -781,22 +850,23 @@ class _XbarNoisyConv(torch.autograd.Function):
     A clipped STE would need per-block saturation masks and is not built.
     ``differential`` selects xbar_diff_fwd_kernel (W+ / W- columns, unipolar
     ADCs), ``dac_bits`` > 0 xbar_serial_fwd_kernel (bit-serial inputs),
-    ``cell_bits`` > 0 xbar_cells_fwd_kernel (bit-sliced weights); the
-    backward is the same."""
+    ``cell_bits`` > 0 xbar_cells_fwd_kernel (bit-sliced weights; with
+    ``cells`` its programmed path, which reads the conductances G of
+    xbar_program_cells in place of the digits); the backward is the same."""
 
     @staticmethod
     def forward(ctx, x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
                 xbar_rows, adc_bits, adc_max, want_telemetry, telemetry_out,
                 current, power_denom, differential=False, in_bits=0,
                 dac_bits=0, x_step=None, w_bits=0, cell_bits=0, w_step=None,
-                w_min=None):
+                w_min=None, cells=None):
         ctx.stride, ctx.padding = stride, padding
         ctx.has_bias = bias is not None
         y, tele = _xbar_forward(x, True, wq, w_raw, bias, stride, padding,
                                 sigma_mode, factor, xbar_rows, adc_bits,
                                 adc_max, want_telemetry, differential,
                                 in_bits, dac_bits, x_step, w_bits, cell_bits,
-                                w_step, w_min)
+                                w_step, w_min, cells)
         if want_telemetry and telemetry_out is not None:
             _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
                           power_denom)
@@ -813,7 +883,7 @@ class _XbarNoisyConv(torch.autograd.Function):
             gw = ConvWgrad.apply(g, x, ctx.stride, ctx.padding, wq.shape, None)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum(dim=(0, 2, 3))
-        return (gx, gw, None, gb) + (None,) * 19
+        return (gx, gw, None, gb) + (None,) * 20
 
 
 class _XbarNoisyLinear(torch.autograd.Function):
@@ -823,13 +893,14 @@ class _XbarNoisyLinear(torch.autograd.Function):
     def forward(ctx, x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
                 adc_bits, adc_max, want_telemetry, telemetry_out, current,
                 power_denom, differential=False, in_bits=0, dac_bits=0,
-                x_step=None, w_bits=0, cell_bits=0, w_step=None, w_min=None):
+                x_step=None, w_bits=0, cell_bits=0, w_step=None, w_min=None,
+                cells=None):
         ctx.has_bias = bias is not None
         y, tele = _xbar_forward(x, False, wq, w_raw, bias, 1, 0, sigma_mode,
                                 factor, xbar_rows, adc_bits, adc_max,
                                 want_telemetry, differential, in_bits,
                                 dac_bits, x_step, w_bits, cell_bits, w_step,
-                                w_min)
+                                w_min, cells)
         if want_telemetry and telemetry_out is not None:
             _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
                           power_denom)
@@ -846,7 +917,7 @@ class _XbarNoisyLinear(torch.autograd.Function):
             gw = LinearWgrad.apply(g, x)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = g.sum(dim=0)
-        return (gx, gw, None, gb) + (None,) * 17
+        return (gx, gw, None, gb) + (None,) * 18
 
 
 def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
@@ -854,7 +925,7 @@ def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
                       power_denom=1.0, want_telemetry=False,
                       telemetry_out=None, differential=False, in_bits=0,
                       dac_bits=0, x_step=None, w_bits=0, cell_bits=0,
-                      w_step=None, w_min=None):
+                      w_step=None, w_min=None, cells=None):
     """Noisy conv on tiled crossbars.
 
     The contraction index is the filter's memory order (r, s, c), c fastest;
@@ -947,32 +1018,50 @@ def xbar_noisy_conv2d(x, wq, w_raw, bias, stride, padding, sigma_mode, factor,
     from the current the cells draw, sum p_bt, not shift-weighted. Not
     combinable with ``differential`` or ``dac_bits``. ``cell_bits`` = 0 is the
     op with one analog cell per weight. The backward is unchanged.
+
+    ``cells`` = G[T, K, R*S*C] (needs ``cell_bits`` > 0) runs the bit-sliced
+    op on PROGRAMMED cells: the tensor xbar_program_cells wrote (conductance
+    variation, stuck-at cells; digit units, the dtype of x) stands in for the
+    ideal digits,
+        p_bt = w_step * sum x*G_t
+        s_bt = max(p_bt, 0)                                           (abs)
+             = max(w_step^2 * sum x*round_to_dtype(G_t^2) + p_bt, 0)  (abs2)
+    and everything from v_bt on, the exact digital offset w_min * X_b
+    included, is the model above. ``wq`` then gives the geometry and the
+    gradients only: the backward stays that of conv2d(x, wq, bias).
+    ``cells`` = None is the ideal-digit op exactly.
     """
     if isinstance(stride, (tuple, list)):
         stride = stride[0]
     if isinstance(padding, (tuple, list)):
         padding = padding[0]
-    cells = ()
+    cells_args = ()
     if cell_bits:
         ref.xbar_check_cell_args(w_bits, cell_bits, w_step, w_min, sigma_mode,
                                  adc_bits, differential, dac_bits)
-        cells = (w_bits, cell_bits, w_step, w_min)
+        cells_args = (w_bits, cell_bits, w_step, w_min)
     elif dac_bits:
         ref.xbar_check_serial_args(in_bits, dac_bits, x_step, x.dtype,
                                    sigma_mode, adc_bits, differential)
+    elif cells is not None:
+        raise ValueError("cells (programmed conductances) needs cell_bits > 0")
     ref.xbar_check_args(sigma_mode, xbar_rows, adc_bits, adc_max)
+    if cells is not None:
+        _check_cells(cells, wq, w_bits, cell_bits)
+        cells_args = cells_args + (cells,)
     return _XbarNoisyConv.apply(x, wq, w_raw, bias, stride, padding,
                                 sigma_mode, factor, xbar_rows, adc_bits,
                                 adc_max, want_telemetry, telemetry_out,
                                 current, power_denom, bool(differential),
-                                in_bits, dac_bits, x_step, *cells)
+                                in_bits, dac_bits, x_step, *cells_args)
 
 
 def xbar_noisy_linear(x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
                       adc_bits, adc_max, current=0.0, power_denom=1.0,
                       want_telemetry=False, telemetry_out=None,
                       differential=False, in_bits=0, dac_bits=0, x_step=None,
-                      w_bits=0, cell_bits=0, w_step=None, w_min=None):
+                      w_bits=0, cell_bits=0, w_step=None, w_min=None,
+                      cells=None):
     """Noisy linear layer on tiled crossbars: xbar_noisy_conv2d with the input
     index as the crossbar row. Same straight-through backward (the gradients
     of F.linear(x, wq, bias)); a clipped STE is out of scope.
@@ -980,21 +1069,27 @@ def xbar_noisy_linear(x, wq, w_raw, bias, sigma_mode, factor, xbar_rows,
     described there (meant for non-negative activations); ``dac_bits`` > 0
     the bit-serial inputs described there (``in_bits``, ``x_step``),
     ``cell_bits`` > 0 the bit-sliced weights described there (``w_bits``,
-    ``w_step``, ``w_min``)."""
-    cells = ()
+    ``w_step``, ``w_min``), ``cells`` = G[T, K, n] the programmed cells
+    described there."""
+    cells_args = ()
     if cell_bits:
         ref.xbar_check_cell_args(w_bits, cell_bits, w_step, w_min, sigma_mode,
                                  adc_bits, differential, dac_bits)
-        cells = (w_bits, cell_bits, w_step, w_min)
+        cells_args = (w_bits, cell_bits, w_step, w_min)
     elif dac_bits:
         ref.xbar_check_serial_args(in_bits, dac_bits, x_step, x.dtype,
                                    sigma_mode, adc_bits, differential)
+    elif cells is not None:
+        raise ValueError("cells (programmed conductances) needs cell_bits > 0")
     ref.xbar_check_args(sigma_mode, xbar_rows, adc_bits, adc_max)
+    if cells is not None:
+        _check_cells(cells, wq, w_bits, cell_bits)
+        cells_args = cells_args + (cells,)
     return _XbarNoisyLinear.apply(x, wq, w_raw, bias, sigma_mode, factor,
                                   xbar_rows, adc_bits, adc_max,
                                   want_telemetry, telemetry_out, current,
                                   power_denom, bool(differential), in_bits,
-                                  dac_bits, x_step, *cells)
+                                  dac_bits, x_step, *cells_args)
 
 
 # ---------------------------------------------------------------------------

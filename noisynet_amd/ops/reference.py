@@ -221,6 +221,58 @@ def xbar_cell_params(w_step, w_min, device):
     return torch.cat([ws, 1.0 / ws, wm])
 
 
+def xbar_check_program_args(sigma, p_stuck_off, p_stuck_on):
+    """Argument rules of the cell model of xbar_program_cells."""
+    if not float(sigma) >= 0:
+        raise ValueError("sigma (cell conductance variation) must be >= 0, "
+                         "got %r" % (sigma,))
+    if not float(p_stuck_off) >= 0:
+        raise ValueError("p_stuck_off must be >= 0, got %r" % (p_stuck_off,))
+    if not float(p_stuck_on) >= 0:
+        raise ValueError("p_stuck_on must be >= 0, got %r" % (p_stuck_on,))
+    if float(p_stuck_off) + float(p_stuck_on) > 1:
+        raise ValueError("p_stuck_off + p_stuck_on must be <= 1, got %r"
+                         % (float(p_stuck_off) + float(p_stuck_on),))
+
+
+def xbar_program_cells(wq, w_bits, cell_bits, cell, sigma=0.0,
+                       p_stuck_off=0.0, p_stuck_on=0.0, gen=None):
+    """Program a layer's weight codes onto imperfect cells: the CPU twin of
+    the HIP kernel xbar_program_cells_kernel. ``wq`` is a conv filter
+    [K, C, R, S] or a linear weight [K, n]; the result is G[T, K, n] in the
+    dtype of ``wq`` with the rows in crossbar order (r, s, c), c fastest:
+        code = clamp(rint((f32(wq) - w_min) * (1/w_step)), 0, 2^B - 1)
+        d_t  = (code >> t*E) & (2^E - 1)
+        d'_t = 0 with probability p_stuck_off (stuck at the high-resistance
+               state), 2^E - 1 with probability p_stuck_on (stuck on: the top
+               level of an E-bit cell), d_t otherwise
+        G_t  = round_to_dtype(max(d'_t * (1 + sigma * z), 0)),  z ~ N(0, 1)
+    in fp32 with the one rounding, one (u, z) pair per cell. The variation is
+    multiplicative and Gaussian, clamped at zero: an off cell stays off and a
+    stuck-on cell varies like any other. Log-normal variation and additive
+    HRS leakage are not modelled. The draws come from ``gen`` (a
+    torch.Generator): the kernel's distribution on another stream."""
+    xbar_check_program_args(sigma, p_stuck_off, p_stuck_on)
+    E, B = int(cell_bits), int(w_bits)
+    T = -(-B // E)
+    wqm = xbar_weight_rows(wq.detach())
+    inv_w_step, w_min = cell[1], cell[2]
+    code = torch.round((wqm.float() - w_min) * inv_w_step)
+    code = code.clamp(0, float(2 ** B - 1)).to(torch.int32)
+    shape = (T,) + tuple(wqm.shape)
+    u = torch.rand(shape, dtype=torch.float32, device=wqm.device,
+                   generator=gen)
+    z = torch.randn(shape, dtype=torch.float32, device=wqm.device,
+                    generator=gen)
+    d = torch.stack([((code >> (t * E)) & (2 ** E - 1)).float()
+                     for t in range(T)])
+    top = float(2 ** E - 1)
+    p_off, p_on = float(p_stuck_off), float(p_stuck_on)
+    d = torch.where(u < p_off, torch.zeros_like(d),
+                    torch.where(u < p_off + p_on, torch.full_like(d, top), d))
+    return (d * (1.0 + float(sigma) * z)).clamp_min(0).to(wq.dtype)
+
+
 def xbar_conv_rows(x, R, S, stride, padding):
     """im2col matrix [N*OH*OW, R*S*C] of an NCHW input with the contraction
     index in the filter's memory order (r, s, c), c fastest -- the crossbar
@@ -241,7 +293,8 @@ def xbar_weight_rows(w):
 
 def xbar_vmm(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows, adc_bits,
              adc, gen=None, stats=None, differential=False, dac=None,
-             in_bits=0, dac_bits=0, cell=None, w_bits=0, cell_bits=0):
+             in_bits=0, dac_bits=0, cell=None, w_bits=0, cell_bits=0,
+             cells=None):
     """Blocked analog VMM on row matrices: xm [M, n], wqm / wrm [K, n].
 
     Block b covers rows [b*xbar_rows, min((b+1)*xbar_rows, n)). Per block
@@ -258,7 +311,10 @@ def xbar_vmm(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows, adc_bits,
     ``differential`` runs every block on two columns (see _xbar_vmm_diff);
     ``dac_bits`` > 0 streams the input in slices (see _xbar_vmm_serial);
     ``cell_bits`` > 0 spreads the weight code over columns (see
-    _xbar_vmm_cells)."""
+    _xbar_vmm_cells); ``cells`` then hands it the programmed conductances
+    G[T, K, n] of xbar_program_cells in place of the ideal digits."""
+    if cells is not None and not cell_bits:
+        raise ValueError("cells (programmed conductances) needs cell_bits > 0")
     if cell_bits:
         if differential or dac_bits:
             raise ValueError("bit-sliced weights (cell_bits > 0) cannot be "
@@ -266,7 +322,7 @@ def xbar_vmm(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows, adc_bits,
                              "bit-serial inputs")
         return _xbar_vmm_cells(xm, wqm, bias, sigma_mode, factor, xbar_rows,
                                adc_bits, adc, cell, w_bits, cell_bits, gen,
-                               stats)
+                               stats, cells)
     if dac_bits:
         if differential:
             raise ValueError("differential columns with bit-serial inputs "
@@ -493,7 +549,8 @@ def _xbar_vmm_serial(xm, wqm, wrm, bias, sigma_mode, factor, xbar_rows,
 
 
 def _xbar_vmm_cells(xm, wqm, bias, sigma_mode, factor, xbar_rows, adc_bits,
-                    adc, cell, w_bits, cell_bits, gen=None, stats=None):
+                    adc, cell, w_bits, cell_bits, gen=None, stats=None,
+                    cells=None):
     """xbar_vmm with bit-sliced weights: a cell holds ``cell_bits`` = E bits,
     so the ``w_bits`` = B bit offset-binary code of a weight on the grid
     w = w_min + code * w_step (``cell`` = [w_step, 1/w_step, w_min] of
@@ -514,9 +571,17 @@ def _xbar_vmm_cells(xm, wqm, bias, sigma_mode, factor, xbar_rows, adc_bits,
     the shift-added noises, max_y the clean shift-added sum with the offset
     and the bias, clipped counts the (b, t) partials with rint(v/step) > Qu or
     < 0, n_partials = T * nblocks * M * K and partial_absmax = max |v_bt| --
-    the figure to size the per-slice, unipolar adc_max from."""
+    the figure to size the per-slice, unipolar adc_max from.
+
+    ``cells`` = G[T, K, n] (xbar_program_cells; digit units, a 16-bit or fp32
+    dtype) replaces the digits: G_t stands for d_t and
+    round_to_dtype(f32(G_t)^2) for d_t^2; nothing else changes."""
     E, B = int(cell_bits), int(w_bits)
     T = -(-B // E)
+    if cells is not None and tuple(cells.shape) != (T,) + tuple(wqm.shape):
+        raise ValueError("cells must have the shape %r (slices, output "
+                         "columns, crossbar rows), got %r"
+                         % ((T,) + tuple(wqm.shape), tuple(cells.shape)))
     w_step, inv_w_step, w_min = cell[0], cell[1], cell[2]
     w_step2 = w_step * w_step
     code = torch.round((wqm.float() - w_min) * inv_w_step)
@@ -542,13 +607,18 @@ def _xbar_vmm_cells(xm, wqm, bias, sigma_mode, factor, xbar_rows, adc_bits,
         xb = xm[:, k0:k1]
         for t in range(T):
             shift = float(2 ** (t * E))
-            dt = ((code[:, k0:k1] >> (t * E)) & (2 ** E - 1)).float()
+            if cells is None:
+                dt = ((code[:, k0:k1] >> (t * E)) & (2 ** E - 1)).float()
+                dt2 = dt * dt
+            else:
+                dt = cells[t][:, k0:k1].float()
+                dt2 = (dt * dt).to(cells.dtype).float()
             p = w_step * (xb @ dt.t())
             v = p
             if sigma_mode is not None:
                 s = p
                 if sigma_mode == "abs2":
-                    s = w_step2 * (xb @ (dt * dt).t()) + p
+                    s = w_step2 * (xb @ dt2.t()) + p
                 s = s.clamp_min(0)
                 eps = torch.randn(p.shape, dtype=torch.float32,
                                   device=p.device, generator=gen)

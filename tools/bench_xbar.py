@@ -34,6 +34,14 @@ and for xbar_rows in {64, 128, 256}:
                 bf16 matmuls (digits and their squares), randn noise, round /
                 clamp and the shift-add, per block the offset; the digit
                 matrices are built once, outside the timed region
+  (g) prog      (f) on programmed cells: ops.xbar_program_cells writes the
+                conductances G once (sigma 0.1, 1 % stuck off, 0.5 % stuck
+                on) and the fused op reads the T slices of G in place of the
+                digits; no one-bit shortcut for the squares. 'program' is
+                the programming kernel on its own
+  (f") eager_prog  (f') given the same G: the slices of G and their squares
+                as the digit matrices. The condition is (g) + program <
+                (f") at every row count
 
 Device events around windows of at least --window seconds after a warm-up,
 the variants alternating over --rounds rounds in one process; the median
@@ -43,7 +51,8 @@ CPU fallback: a time is a GPU time or it is not reported.
 --resource-usage needs no GPU: it compiles csrc/conv_mfma.hip for gfx950 with
 -Rpass-analysis=kernel-resource-usage and prints VGPRs, LDS and scratch of
 every xbar_fwd_kernel, xbar_diff_fwd_kernel, xbar_serial_fwd_kernel and
-xbar_cells_fwd_kernel instantiation.
+xbar_cells_fwd_kernel instantiation (the programmed-cell ones, PROG, listed
+apart) and of xbar_program_cells_kernel.
 """
 
 import argparse
@@ -77,6 +86,8 @@ W_BITS, W_RANGE, CELL_BITS = 4, (-0.3, 0.3), (1, 2)
 W_STEP = (W_RANGE[1] - W_RANGE[0]) / (2 ** W_BITS - 1)
 # the range [0, adc_max] of one unipolar slice conversion
 CELL_ADC_MAX = 4.0
+# programmed cells: conductance variation and stuck-at rates of the chip
+CELL_VAR, CELL_P_OFF, CELL_P_ON = 0.1, 0.01, 0.005
 
 
 def eager_blocked(xm, wq, fw, factor, xbar_rows, step, inv_step, qm,
@@ -331,6 +342,7 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
         step_c, inv_step_c = adc_c[0], adc_c[1]
         ckw = dict(w_bits=W_BITS, w_step=W_STEP, w_min=W_RANGE[0])
         digits, squares, moved_cells = {}, {}, {}
+        chips, chip_rows, chip_squares, moved_prog = {}, {}, {}, {}
         for E in CELL_BITS:
             digits[E] = make_digits(wg_rows, W_STEP, W_RANGE[0], W_BITS, E)
             squares[E] = [(d * d).contiguous() for d in digits[E]]
@@ -356,6 +368,45 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
 
             variants['cells_e%d' % E] = run_cells
             variants['eager_cells_e%d' % E] = run_eager_cells
+            # the same on programmed cells
+            pkw = dict(sigma=CELL_VAR, p_stuck_off=CELL_P_OFF,
+                       p_stuck_on=CELL_P_ON, seed=1)
+            chips[E] = ops.xbar_program_cells(wg, W_BITS, E, W_STEP,
+                                              W_RANGE[0], **pkw)
+            chip_rows[E] = [g.contiguous() for g in chips[E]]
+            chip_squares[E] = [(g.float() * g.float()).to(dtype)
+                               for g in chip_rows[E]]
+
+            def run_prog(E=E):
+                for _ in range(reps):
+                    if conv:
+                        ops.xbar_noisy_conv2d(x, wg, wg, None, 1, 0, MODE,
+                                              factor, rows, ADC_BITS,
+                                              CELL_ADC_MAX, cell_bits=E,
+                                              cells=chips[E], **ckw)
+                    else:
+                        ops.xbar_noisy_linear(x, wg, wg, None, MODE, factor,
+                                              rows, ADC_BITS, CELL_ADC_MAX,
+                                              cell_bits=E, cells=chips[E],
+                                              **ckw)
+                return reps
+
+            def run_program(E=E):
+                for _ in range(reps):
+                    ops.xbar_program_cells(wg, W_BITS, E, W_STEP, W_RANGE[0],
+                                           **pkw)
+                return reps
+
+            def run_eager_prog(E=E):
+                xm = ref.xbar_conv_rows(x, spec['w'][2], spec['w'][3], 1, 0) \
+                    if conv else x
+                eager_cells(xm, chip_rows[E], chip_squares[E], factor, rows,
+                            step_c, inv_step_c, qu, cell[0], cell[2], E)
+                return 1
+
+            variants['prog_e%d' % E] = run_prog
+            variants['program_e%d' % E] = run_program
+            variants['eager_prog_e%d' % E] = run_eager_prog
         with torch.no_grad():
             # results must agree before speeds are compared: noise off, the
             # fused op against the eager composition on the same blocks
@@ -428,6 +479,24 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
                 diff = (a.float() - e.to(a.dtype).float()).abs()
                 moved_cells[E] = float(
                     (diff > 0.5 * float(step_c)).float().mean())
+                if conv:
+                    a = ops.xbar_noisy_conv2d(x, wg, wg, None, 1, 0, None, 0.0,
+                                              rows, ADC_BITS, CELL_ADC_MAX,
+                                              cell_bits=E, cells=chips[E],
+                                              **ckw)
+                    a = a.permute(0, 2, 3, 1).reshape(-1, a.shape[1])
+                else:
+                    a = ops.xbar_noisy_linear(x, wg, wg, None, None, 0.0,
+                                              rows, ADC_BITS, CELL_ADC_MAX,
+                                              cell_bits=E, cells=chips[E],
+                                              **ckw)
+                e = eager_cells(xm, chip_rows[E], chip_squares[E],
+                                torch.zeros(1, device=dev), rows, step_c,
+                                inv_step_c, qu, cell[0], cell[2], E,
+                                fp32_matmul=True)
+                diff = (a.float() - e.to(a.dtype).float()).abs()
+                moved_prog[E] = float(
+                    (diff > 0.5 * float(step_c)).float().mean())
             del xm
             for fn in variants.values():    # warm-up: code objects, allocator
                 fn()
@@ -476,7 +545,21 @@ def bench_layer(name, spec, rows_list, window, rounds, reps):
             res['eager_cells_e%d_over_cells' % E] = round(eag / cel, 2)
             res['cells_e%d_noise_off_outputs_off_by_a_step_vs_eager' % E] = \
                 moved_cells[E]
-        del slices, digits, squares
+        res.update(cell_var=CELL_VAR, cell_stuck_off=CELL_P_OFF,
+                   cell_stuck_on=CELL_P_ON)
+        for E in CELL_BITS:
+            prg, one = sec['prog_e%d' % E], sec['program_e%d' % E]
+            eag = sec['eager_prog_e%d' % E]
+            res['prog_e%d_ms' % E] = round(prg * 1e3, 4)
+            res['program_e%d_ms' % E] = round(one * 1e3, 4)
+            res['eager_prog_e%d_ms' % E] = round(eag * 1e3, 4)
+            res['prog_e%d_over_cells' % E] = round(
+                prg / sec['cells_e%d' % E], 3)
+            res['eager_prog_e%d_over_prog_plus_program' % E] = round(
+                eag / (prg + one), 2)
+            res['prog_e%d_noise_off_outputs_off_by_a_step_vs_eager' % E] = \
+                moved_prog[E]
+        del slices, digits, squares, chips, chip_rows, chip_squares
         print(json.dumps(res), flush=True)
         results.append(res)
     return results
@@ -511,7 +594,8 @@ def parse_resource_usage(text):
                 if ('xbar_fwd_kernel' in m.group(1)
                     or 'xbar_diff_fwd_kernel' in m.group(1)
                     or 'xbar_serial_fwd_kernel' in m.group(1)
-                    or 'xbar_cells_fwd_kernel' in m.group(1)) else None
+                    or 'xbar_cells_fwd_kernel' in m.group(1)
+                    or 'xbar_program_cells_kernel' in m.group(1)) else None
             if cur is not None:
                 rows.append(cur)
             continue
@@ -529,10 +613,14 @@ def parse_resource_usage(text):
     # top of the static bytes reported above
     diff = [r for r in rows if 'xbar_diff_fwd_kernel' in r['kernel']]
     serial = [r for r in rows if 'xbar_serial_fwd_kernel' in r['kernel']]
-    cells = [r for r in rows if 'xbar_cells_fwd_kernel' in r['kernel']]
+    # the trailing template flag PROG (programmed cells) is the fourth ELb
+    all_cells = [r for r in rows if 'xbar_cells_fwd_kernel' in r['kernel']]
+    cells = [r for r in all_cells if r['kernel'].split('ELb')[3][0] == '0']
+    prog = [r for r in all_cells if r['kernel'].split('ELb')[3][0] == '1']
+    program = [r for r in rows if 'xbar_program_cells_kernel' in r['kernel']]
     summarise('xbar_fwd_kernel',
               [r for r in rows if r not in diff and r not in serial
-               and r not in cells], 256)
+               and r not in all_cells and r not in program], 256)
     summarise('xbar_diff_fwd_kernel', diff, 384)
     # (J*64 + 3*64) rows; the mangled name carries T (DF16b / DF16_ / f), J,
     # SIGMA_MODE, ADC and TELEM as I<T>Li<J>ELi<mode>ELb<adc>ELb<telem>E
@@ -553,6 +641,16 @@ def parse_resource_usage(text):
                   and 'kernelIf' not in r['kernel']]
         summarise('xbar_cells_fwd_kernel T=%d, 16-bit, no telemetry' % T,
                   steady, 64 + 128 * T)
+    # programmed cells: the same tiles, read from G instead of derived
+    for T in (1, 2, 3, 4):
+        of_t = [r for r in prog
+                if re.search(r'kernelI\w+?Li%dELi\dELb' % T, r['kernel'])]
+        summarise('xbar_cells_fwd_kernel PROG T=%d' % T, of_t, 64 + 128 * T)
+        steady = [r for r in of_t if r['kernel'].split('ELb')[2][0] == '0'
+                  and 'kernelIf' not in r['kernel']]
+        summarise('xbar_cells_fwd_kernel PROG T=%d, 16-bit, no telemetry' % T,
+                  steady, 64 + 128 * T)
+    summarise('xbar_program_cells_kernel', program, 0)
     return rows
 
 
@@ -604,6 +702,10 @@ def main():
                 if not r['cells_e%d_ms' % E] < r['eager_cells_e%d_ms' % E]:
                     slower.append((name, r['xbar_rows'],
                                    'bit-sliced cell_bits %d' % E))
+                if not (r['prog_e%d_ms' % E] + r['program_e%d_ms' % E]
+                        < r['eager_prog_e%d_ms' % E]):
+                    slower.append((name, r['xbar_rows'],
+                                   'programmed cells cell_bits %d' % E))
     if slower:
         raise SystemExit('fused op not faster than the eager composition at '
                          '%s' % slower)
