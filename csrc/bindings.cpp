@@ -164,6 +164,7 @@ std::vector<torch::Tensor> sigma_noise_linear_impl(torch::Tensor x,
                                                    int64_t seed,
                                                    bool telem);
 
+// xbar_fwd.hip
 // tiled crossbars (per-block noise + ADC); adc = fp32 [step, 1/step]
 std::vector<torch::Tensor> xbar_fwd_conv(
     torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
@@ -184,6 +185,7 @@ std::vector<torch::Tensor> xbar_diff_fwd_linear(
     int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
     int64_t adc_bits, torch::Tensor adc, int64_t seed, bool telem);
 
+// xbar_serial.hip
 // bit-serial inputs: in_bits-bit codes on the grid x_step, dac_bits per slice;
 // dac = fp32 [x_step, 1/x_step]
 std::vector<torch::Tensor> xbar_serial_fwd_conv(
@@ -197,6 +199,7 @@ std::vector<torch::Tensor> xbar_serial_fwd_linear(
     int64_t adc_bits, torch::Tensor adc, int64_t in_bits, int64_t dac_bits,
     torch::Tensor dac, int64_t seed, bool telem);
 
+// xbar_cells.hip
 // bit-sliced weights: w_bits-bit offset-binary codes on the grid
 // w_min + code * w_step, cell_bits per column, unipolar per-column ADCs;
 // cell = fp32 [w_step, 1/w_step, w_min]
@@ -229,6 +232,7 @@ torch::Tensor xbar_program_cells(torch::Tensor wq, int64_t w_bits,
                                  double sigma, double p_stuck_off,
                                  double p_stuck_on, int64_t seed, bool fresh);
 
+// conv_mfma.hip
 std::string conv_fused_route(int64_t C, int64_t H, int64_t W, int64_t K,
                              int64_t R, int64_t S, int64_t stride, int64_t pad,
                              int64_t elem_size);

@@ -21,157 +21,16 @@
 //     ds_read_b128 fragment reads avoid the row-power-of-2 bank pattern
 //   * fp32 path uses v_mfma_f32_16x16x4_f32 (exact f32, for unit tests)
 //
-// A/B/C fragment maps for v_mfma_f32_16x16x32_bf16 (cdna_hip_programming.md
-// §3): A[i][k]: i = lane&15, k = 8*(lane>>4)+j (j=0..7, 8 bf16 = 4 VGPRs);
-// B[k][j]: j = lane&15, same k split; C/D: col = lane&15,
-// row = 4*(lane>>4) + reg.
+// The tile abstraction (Mma<T>, with the A/B/C fragment maps) and ConvGeom
+// live in mfma_tile.h; the crossbar kernels (xbar_*.hip) share them.
 
-#include <torch/extension.h>
-#include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include "common.h"
+#include "mfma_tile.h"
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int BM = 64;
-constexpr int BN = 64;
-constexpr int BK = 32;
-
-using bf16 = __hip_bfloat16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x8 = __attribute__((ext_vector_type(8))) float;
-
-// ---------------------------------------------------------------------------
-// Compute-type traits: one MFMA tile abstraction per input dtype.
-//   bf16 -> v_mfma_f32_16x16x32_bf16 (8 bf16/lane fragments)
-//   fp16 -> v_mfma_f32_16x16x32_f16
-//   fp32 -> v_mfma_f32_16x16x4_f32 x8 (EXACT f32 at the f32 vector rate --
-//           gfx950 has no xf32; cdna_hip_programming.md §3). The f32 LDS
-//           image stores k at permuted position (k&3)*8 + (k>>2) so each
-//           lane's 8 needed elements (k = q + 4*kk, q = lane>>4) are the
-//           contiguous span [q*8, q*8+8) -> one 32-B read.
-// All three share the C/D fragment map (dtype-independent on gfx950), so
-// accumulators and epilogues are identical.
-// ---------------------------------------------------------------------------
-
-template <typename T> struct Mma;
-
-template <> struct Mma<bf16> {
-  using frag = bf16x8;
-  static constexpr int STRIDE = 80;   // 32 el * 2 B + 16 B skew
-  static DEV_INLINE void store8(char* lds, int row, int k0, const float* v) {
-    bf16 tmp[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) tmp[j] = __float2bfloat16(v[j]);
-    *(bf16x8*)(lds + row * STRIDE + k0 * 2) = *(bf16x8*)tmp;
-  }
-  static DEV_INLINE frag load(char* lds, int row, int lane) {
-    return *(frag*)(lds + row * STRIDE + (lane >> 4) * 16);
-  }
-  static DEV_INLINE void mma(const frag& a, const frag& b, f32x4& acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-  }
-  static DEV_INLINE void store1(char* lds, int row, int k, float v) {
-    *(bf16*)(lds + row * STRIDE + k * 2) = __float2bfloat16(v);
-  }
-  static DEV_INLINE void store1n(char* lds, int row, int k, bf16 v) {
-    *(bf16*)(lds + row * STRIDE + k * 2) = v;
-  }
-  // read the lane's fragment from a RAW 32-element span (no tile rows)
-  static DEV_INLINE frag load_span(const char* base, int lane) {
-    return *(frag*)(base + (lane >> 4) * 16);
-  }
-};
-
-template <> struct Mma<_Float16> {
-  using frag = f16x8;
-  static constexpr int STRIDE = 80;
-  static DEV_INLINE void store8(char* lds, int row, int k0, const float* v) {
-    _Float16 tmp[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) tmp[j] = (_Float16)v[j];
-    *(f16x8*)(lds + row * STRIDE + k0 * 2) = *(f16x8*)tmp;
-  }
-  static DEV_INLINE frag load(char* lds, int row, int lane) {
-    return *(frag*)(lds + row * STRIDE + (lane >> 4) * 16);
-  }
-  static DEV_INLINE void mma(const frag& a, const frag& b, f32x4& acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
-  }
-  static DEV_INLINE void store1(char* lds, int row, int k, float v) {
-    *(_Float16*)(lds + row * STRIDE + k * 2) = (_Float16)v;
-  }
-  static DEV_INLINE void store1n(char* lds, int row, int k, _Float16 v) {
-    *(_Float16*)(lds + row * STRIDE + k * 2) = v;
-  }
-  static DEV_INLINE frag load_span(const char* base, int lane) {
-    return *(frag*)(base + (lane >> 4) * 16);
-  }
-};
-
-template <> struct Mma<float> {
-  using frag = f32x8;
-  static constexpr int STRIDE = 144;  // 32 el * 4 B + 16 B skew
-  static DEV_INLINE void store8(char* lds, int row, int k0, const float* v) {
-    float* base = (float*)(lds + row * STRIDE);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      int k = k0 + j;
-      base[((k & 3) << 3) + (k >> 2)] = v[j];
-    }
-  }
-  static DEV_INLINE frag load(char* lds, int row, int lane) {
-    return *(frag*)(lds + row * STRIDE + (lane >> 4) * 32);
-  }
-  static DEV_INLINE void mma(const frag& a, const frag& b, f32x4& acc) {
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk)
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], b[kk], acc, 0, 0, 0);
-  }
-  static DEV_INLINE void store1(char* lds, int row, int k, float v) {
-    ((float*)(lds + row * STRIDE))[((k & 3) << 3) + (k >> 2)] = v;
-  }
-  static DEV_INLINE void store1n(char* lds, int row, int k, float v) {
-    store1(lds, row, k, v);
-  }
-  static DEV_INLINE frag load_span(const char* base, int lane) {
-    // raw span is k-linear: gather the lane's strided k = q + 4*kk
-    frag f;
-    int q = lane >> 4;
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk)
-      f[kk] = ((const float*)base)[q + 4 * kk];
-    return f;
-  }
-};
-
-DEV_INLINE float atomic_max_f32(float* addr, float val) {
-  // monotone int mapping for IEEE floats
-  int* ia = (int*)addr;
-  int old = __float_as_int(val);
-  if (val >= 0.0f) {
-    return __int_as_float(atomicMax(ia, old));
-  }
-  return __uint_as_float(atomicMin((unsigned int*)ia, (unsigned int)old));
-}
-
-struct ConvGeom {
-  int N, H, W, C;      // input
-  int K, R, S;         // filter
-  int OH, OW;          // output
-  int stride, pad;
-  int64_t M;           // = N*OH*OW rows of the implicit GEMM
-  int flat;            // 1: contraction runs over flattened (r,s,c) in one
-                       // K-loop (small-C layers: conv1's C=3 would otherwise
-                       // waste 90% of each 32-deep MFMA K-step per tap)
-  int Kw;     // rows readable in the weight tensor (host may row-pad)
-};
 
 // --------------------------------------------------------------------------
 // Staging helpers: global (NHWC) -> LDS tile [rows][BK], bf16, skewed rows.
@@ -1488,32 +1347,6 @@ bool ww_forced_legacy() {
   return e != nullptr && std::string(e) == "legacy";
 }
 
-template <typename scalar_t> struct DevT { using type = scalar_t; };
-template <> struct DevT<at::BFloat16> { using type = __hip_bfloat16; };
-template <> struct DevT<at::Half> { using type = _Float16; };
-
-ConvGeom make_geom(int N, int H, int W, int C, int K, int R, int S, int stride,
-                   int pad) {
-  ConvGeom g;
-  g.N = N; g.H = H; g.W = W; g.C = C; g.K = K; g.R = R; g.S = S;
-  g.Kw = K;  // weight rows staged-safe (== K unless the host row-pads)
-  g.stride = stride; g.pad = pad;
-  g.OH = (H + 2 * pad - R) / stride + 1;
-  g.OW = (W + 2 * pad - S) / stride + 1;
-  g.M = (int64_t)N * g.OH * g.OW;
-  // flatten the contraction when per-tap C wastes most of a 32-deep K-step
-  g.flat = (C < 16 && R * S > 1) ? 1 : 0;
-  return g;
-}
-
-// NHWC raw pointer views of channels_last tensors
-inline void check_cl(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast),
-              name, ": expected 4-D channels_last tensor");
-}
-
-void check_sigma_mode(int64_t sigma_mode, bool allow_zero, const char* who);
-
 }  // namespace
 
 // ===========================================================================
@@ -1692,14 +1525,6 @@ torch::Tensor conv_wgrad(torch::Tensor gy, torch::Tensor x, int64_t stride,
 // the conv kernels run unchanged on raw pointers.
 // ===========================================================================
 
-namespace {
-ConvGeom linear_geom(const torch::Tensor& x, int64_t out_features) {
-  TORCH_CHECK(x.dim() == 2 && x.is_contiguous(), "linear: 2-D contiguous");
-  return make_geom((int)x.size(0), 1, 1, (int)x.size(1), (int)out_features,
-                   1, 1, 1, 0);
-}
-}  // namespace
-
 torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w) {
   TORCH_CHECK(w.dim() == 2 && w.is_contiguous());
   auto g = linear_geom(x, w.size(0));
@@ -1815,15 +1640,20 @@ bool smallk_eligible(const torch::Tensor& x, int64_t K) {
          LinearRoute::SmallK;
 }
 
+}  // namespace
+
 // The fused kernels are instantiated for sigma_mode 1 (|w|) and 2
 // (|w|^2+|w|); a noise-free mode 0 exists only where allow_zero says so.
-// Anything else used to fall through to the mode-2 launch.
+// Anything else used to fall through to the mode-2 launch. (Declared in
+// mfma_tile.h: the crossbar translation units call it too.)
 void check_sigma_mode(int64_t sigma_mode, bool allow_zero, const char* who) {
   TORCH_CHECK(sigma_mode == 1 || sigma_mode == 2 ||
                   (allow_zero && sigma_mode == 0),
               who, ": sigma_mode ", sigma_mode, " is not supported here (",
               allow_zero ? "0, " : "", "1 or 2)");
 }
+
+namespace {
 
 std::vector<torch::Tensor> linear_fwd_fused_smallk(
     torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
@@ -3541,1921 +3371,4 @@ torch::Tensor conv_wgrad_from_col(torch::Tensor gy, torch::Tensor col,
                 .permute({0, 3, 1, 2})
                 .contiguous(at::MemoryFormat::ChannelsLast);
   return dw;
-}
-
-// ===========================================================================
-// Tiled crossbars: per-block current noise and ADC in one fused MFMA VMM.
-//
-// The contraction (crossbar rows) runs over the flat (r, s, c) filter order,
-// c fastest -- for a linear layer the input index -- and is cut into blocks
-// of xbar_rows rows (a positive multiple of the 32-row k-step; the last block
-// may be short). Per block b and output (m, k):
-//   p_b = sum x * wq                  s_b = max(sum x * f(|w_raw|), 0)
-//   v_b = p_b + eps_b * sqrt(factor * s_b)       eps_b ~ N(0,1) per block
-//   q_b = step * clamp(rint(v_b * inv_step), -Qm, Qm)
-//   out = sum_b q_b + bias            (fp32, b ascending; rounded once)
-// The block epilogue runs in registers on the live 2x2 accumulator fragments
-// every xbar_rows/32 k-steps; no partial sum reaches memory. The Philox
-// counter of a four-row group is (b*M + m)*K + k, so block 0 draws what the
-// unblocked kernels draw and every block has counters of its own.
-// Same 64x64 tile / 4 waves / BK = 32 structure as conv_fwd_kernel.
-// ===========================================================================
-
-namespace {
-
-// The output pixel a thread stages (fixed for the whole contraction) and the
-// (r, s, c) position of the first of its 8 crossbar rows in the current
-// k-step, advanced by 32 rows per step without a division.
-struct XbarRow {
-  bool live;        // pixel inside M
-  int img, ih0, iw0;
-  int r, s, c;
-};
-
-DEV_INLINE void xbar_row_advance(XbarRow& p, const ConvGeom& g, int rows) {
-  p.c += rows;
-  while (p.c >= g.C) {
-    p.c -= g.C;
-    if (++p.s == g.S) {
-      p.s = 0;
-      ++p.r;
-    }
-  }
-}
-
-// One thread's share of a k-step, held in registers between its global loads
-// and its LDS stores so the next step's loads fly under this step's MFMAs:
-// 8 activations, 8 wq and 8 w_raw elements.
-template <typename T>
-struct XbarRegs {
-  alignas(16) T x[8];
-  alignas(16) T q[8];
-  alignas(16) T w[8];
-};
-
-// activations: 8 consecutive crossbar rows from (r, s, c) on of the thread's
-// output pixel. A span inside one filter tap is 16 contiguous bytes for a
-// 16-bit dtype: one load (memcpy form, since for C % 8 != 0 the address is
-// only element-aligned). A span that straddles taps, or runs past the last
-// row (r reaches R), walks element by element; padding positions are zeros.
-template <typename T>
-DEV_INLINE void xbar_load_x(T (&v)[8], const T* __restrict__ x,
-                            const ConvGeom& g, const XbarRow& p) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = from_f32<T>(0.0f);
-  if (!(p.live && p.r < g.R)) return;
-  if (p.c + 8 <= g.C) {
-    int ih = p.ih0 + p.r, iw = p.iw0 + p.s;
-    if (ih >= 0 && ih < g.H && iw >= 0 && iw < g.W) {
-      const T* px = x + (((int64_t)p.img * g.H + ih) * g.W + iw) * g.C + p.c;
-      if (sizeof(T) == 2) {
-        __builtin_memcpy(v, px, 16);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = px[j];
-      }
-    }
-  } else {
-    int r = p.r, s = p.s, c = p.c;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      int ih = p.ih0 + r, iw = p.iw0 + s;
-      if (r < g.R && ih >= 0 && ih < g.H && iw >= 0 && iw < g.W)
-        v[j] = x[(((int64_t)p.img * g.H + ih) * g.W + iw) * g.C + c];
-      if (++c == g.C) {
-        c = 0;
-        if (++s == g.S) {
-          s = 0;
-          ++r;
-        }
-      }
-    }
-  }
-}
-
-// weights from the [K, pitch] row matrices. For 16-bit dtypes the host pads
-// rows with zeros to pitch % 8 == 0, so every 8-span is one aligned 16-byte
-// load or lies wholly past the row.
-template <typename T, int SIGMA_MODE>
-DEV_INLINE void xbar_load_w(T (&q)[8], T (&w)[8], const T* __restrict__ wq,
-                            const T* __restrict__ wraw, int K, int n0, int ck,
-                            int nrows, int pitch) {
-  int k = n0 + (threadIdx.x >> 2);
-  int c0 = ck + (threadIdx.x & 3) * 8;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    q[j] = from_f32<T>(0.0f);
-    w[j] = from_f32<T>(0.0f);
-  }
-  if (k >= K) return;
-  const T* pq = wq + (int64_t)k * pitch + c0;
-  const T* pr = wraw + (int64_t)k * pitch + c0;
-  if (sizeof(T) == 2 && (pitch & 7) == 0) {
-    if (c0 + 8 <= pitch) {
-      *(bf16x8*)q = *(const bf16x8*)pq;
-      if (SIGMA_MODE > 0) *(bf16x8*)w = *(const bf16x8*)pr;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (c0 + j < nrows) {
-        q[j] = pq[j];
-        if (SIGMA_MODE > 0) w[j] = pr[j];
-      }
-    }
-  }
-}
-
-template <typename T>
-DEV_INLINE void xbar_put8(char* lds, int row, int seg, const T (&v)[8]) {
-  if (sizeof(T) == 2) {
-    *(bf16x8*)(lds + row * Mma<T>::STRIDE + seg * 16) = *(const bf16x8*)v;
-  } else {
-    float f[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = to_f32(v[j]);
-    Mma<T>::store8(lds, row, seg * 8, f);
-  }
-}
-
-// registers -> LDS tiles: x and wq as they are, f(|w_raw|) and (telemetry
-// with abs2) |w_raw| derived from the ONE raw-weight load
-template <typename T, int SIGMA_MODE, bool TELEM>
-DEV_INLINE void xbar_store_tiles(char* a_lds, char* b_lds, char* c_lds,
-                                 char* d_lds, const XbarRegs<T>& rg) {
-  int row = threadIdx.x >> 2;
-  int seg = threadIdx.x & 3;
-  xbar_put8<T>(a_lds, row, seg, rg.x);
-  xbar_put8<T>(b_lds, row, seg, rg.q);
-  if (SIGMA_MODE > 0) {
-    float a[8], v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      a[j] = fabsf(to_f32(rg.w[j]));
-      v[j] = (SIGMA_MODE == 2) ? a[j] * a[j] + a[j] : a[j];
-    }
-    Mma<T>::store8(c_lds, row, seg * 8, v);
-    if (TELEM && SIGMA_MODE == 2) Mma<T>::store8(d_lds, row, seg * 8, a);
-  }
-}
-
-// SIGMA_MODE: 0 noise off, 1 abs, 2 abs2     ADC: quantise every block
-// TELEM: telem[5] = sum sigma_abs, sum |sum_b noise_b|, max clean y,
-//        (unused, see sat_count), max |v_b|; sat_count = number of block
-//        partials with |rint(v_b / step)| > Qm (exact, 64-bit)
-template <typename T, int SIGMA_MODE, bool ADC, bool TELEM, bool BIAS>
-__global__ __launch_bounds__(kBlock)
-void xbar_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
-                     const T* __restrict__ wraw,
-                     const float* __restrict__ bias, T* __restrict__ out,
-                     ConvGeom g, int wpitch, int xbar_rows,
-                     const float* __restrict__ factor_p,
-                     const float* __restrict__ adc_p /* step, 1/step */,
-                     float qm, uint64_t seed, float* __restrict__ telem,
-                     unsigned long long* __restrict__ sat_count,
-                     const int64_t* __restrict__ seed_base) {
-  seed = graph_seed(seed_base, seed);
-  const float factor = (SIGMA_MODE > 0) ? factor_p[0] : 0.0f;
-  const float step = ADC ? adc_p[0] : 1.0f;
-  const float inv_step = ADC ? adc_p[1] : 1.0f;
-  int n0 = blockIdx.x * BN;
-  int64_t m0 = (int64_t)blockIdx.y * BM;
-
-  constexpr int STR = Mma<T>::STRIDE;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* a_lds = smem;                          // BM rows (x)
-  char* b_lds = smem + BM * STR;               // BN rows (wq)
-  char* c_lds = smem + (BM + BN) * STR;        // BN rows (f(|w_raw|))
-  char* d_lds = smem + (BM + 2 * BN) * STR;    // BN rows (|w_raw|, telem)
-
-  int wid = threadIdx.x / WAVE;
-  int wm = wid >> 1, wn = wid & 1;
-  int lane = threadIdx.x & (WAVE - 1);
-
-  // the output pixel this thread stages, decomposed once, and where its
-  // first 8-row span starts
-  XbarRow xr;
-  {
-    int64_t sm = m0 + (threadIdx.x >> 2);
-    xr.live = sm < g.M;
-    int oh = 0, ow = 0;
-    xr.img = 0;
-    if (xr.live) {
-      int64_t t = sm;
-      ow = (int)(t % g.OW); t /= g.OW;
-      oh = (int)(t % g.OH); t /= g.OH;
-      xr.img = (int)t;
-    }
-    xr.ih0 = oh * g.stride - g.pad;
-    xr.iw0 = ow * g.stride - g.pad;
-    xr.r = xr.s = xr.c = 0;
-    xbar_row_advance(xr, g, (threadIdx.x & 3) * 8);
-  }
-
-  f32x4 acc[2][2] = {};     // p_b
-  f32x4 sacc[2][2] = {};    // s_b
-  f32x4 tacc[2][2] = {};    // sigma_abs of the block (telemetry, abs2)
-  f32x4 oacc[2][2] = {};    // sum_b q_b
-  f32x4 ycl[2][2] = {};     // sum_b p_b (telemetry)
-  f32x4 ntot[2][2] = {};    // sum_b noise_b (telemetry)
-  float t_sum_sigma = 0.0f, t_sat = 0.0f, t_vmax = 0.0f;
-
-  const int nrows = g.R * g.S * g.C;
-  const int steps_per_block = xbar_rows / BK;
-  int steps_left = steps_per_block;
-  int b = 0;
-  XbarRegs<T> rg;
-  xbar_load_x(rg.x, x, g, xr);
-  xbar_load_w<T, SIGMA_MODE>(rg.q, rg.w, wq, wraw, g.K, n0, 0, nrows, wpitch);
-  for (int ck = 0; ck < nrows; ck += BK) {
-    xbar_store_tiles<T, SIGMA_MODE, TELEM>(a_lds, b_lds, c_lds, d_lds, rg);
-    __syncthreads();
-    if (ck + BK < nrows) {  // next step's loads, in flight under the MFMAs
-      xbar_row_advance(xr, g, BK);
-      xbar_load_x(rg.x, x, g, xr);
-      xbar_load_w<T, SIGMA_MODE>(rg.q, rg.w, wq, wraw, g.K, n0, ck + BK,
-                                 nrows, wpitch);
-    }
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-      auto a = Mma<T>::load(a_lds, wm * 32 + fm * 16 + (lane & 15), lane);
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-        int brow = wn * 32 + fn * 16 + (lane & 15);
-        auto bq = Mma<T>::load(b_lds, brow, lane);
-        Mma<T>::mma(a, bq, acc[fm][fn]);
-        if (SIGMA_MODE > 0) {
-          auto bs = Mma<T>::load(c_lds, brow, lane);
-          Mma<T>::mma(a, bs, sacc[fm][fn]);
-        }
-        if (TELEM && SIGMA_MODE == 2) {
-          auto bt = Mma<T>::load(d_lds, brow, lane);
-          Mma<T>::mma(a, bt, tacc[fm][fn]);
-        }
-      }
-    }
-    __syncthreads();
-
-    if (--steps_left > 0 && ck + BK < nrows) continue;
-    // block boundary (or the end): noise + ADC on the live fragments
-    steps_left = steps_per_block;
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-        int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
-        int n = n0 + wn * 32 + fn * 16 + (lane & 15);
-        float g4[4];
-        if (SIGMA_MODE > 0)
-          gauss4(seed, (uint64_t)(((int64_t)b * g.M + mb) * g.K + n), g4);
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          float p = acc[fm][fn][reg];
-          float v = p;
-          if (SIGMA_MODE > 0) {
-            float sig = fmaxf(sacc[fm][fn][reg], 0.0f);
-            float noise = g4[reg] * sqrtf(factor * sig);
-            v = p + noise;
-            if (TELEM) {
-              ntot[fm][fn][reg] += noise;
-              if (mb + reg < g.M && n < g.K)
-                t_sum_sigma += (SIGMA_MODE == 2) ? tacc[fm][fn][reg]
-                                                 : sacc[fm][fn][reg];
-            }
-          }
-          float q = v;
-          if (ADC) {
-            float t = rintf(v * inv_step);
-            if (TELEM && mb + reg < g.M && n < g.K && fabsf(t) > qm)
-              t_sat += 1.0f;
-            q = step * fminf(fmaxf(t, -qm), qm);
-          }
-          if (TELEM) {
-            ycl[fm][fn][reg] += p;
-            if (mb + reg < g.M && n < g.K) t_vmax = fmaxf(t_vmax, fabsf(v));
-          }
-          oacc[fm][fn][reg] += q;
-        }
-        acc[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        sacc[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        tacc[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      }
-    }
-    ++b;
-  }
-
-  // bias, the one rounding to the dtype, stores
-  float t_sum_noise = 0.0f, t_max_y = -INFINITY;
-#pragma unroll
-  for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-      int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
-      int n = n0 + wn * 32 + fn * 16 + (lane & 15);
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        int64_t m = mb + reg;
-        if (m < g.M && n < g.K) {
-          float bv = BIAS ? bias[n] : 0.0f;
-          out[m * g.K + n] = from_f32<T>(oacc[fm][fn][reg] + bv);
-          if (TELEM) {
-            t_sum_noise += fabsf(ntot[fm][fn][reg]);
-            t_max_y = fmaxf(t_max_y, ycl[fm][fn][reg] + bv);
-          }
-        }
-      }
-    }
-  }
-  if (TELEM) {
-    __shared__ float red[4];
-    __shared__ float redm[2][4];
-    float s0 = block_sum(t_sum_sigma, red);
-    __syncthreads();
-    float s1 = block_sum(t_sum_noise, red);
-    __syncthreads();
-    float s3 = block_sum(t_sat, red);  // <= 4096 per epilogue: exact
-    float my = wave_max(t_max_y);
-    float mv = wave_max(t_vmax);
-    if (lane == 0) {
-      redm[0][wid] = my;
-      redm[1][wid] = mv;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      if (SIGMA_MODE > 0) {
-        atomicAdd(&telem[0], s0);
-        atomicAdd(&telem[1], s1);
-      }
-      atomic_max_f32(&telem[2], fmaxf(fmaxf(redm[0][0], redm[0][1]),
-                                      fmaxf(redm[0][2], redm[0][3])));
-      if (ADC) atomicAdd(sat_count, (unsigned long long)(s3 + 0.5f));
-      atomic_max_f32(&telem[4], fmaxf(fmaxf(redm[1][0], redm[1][1]),
-                                      fmaxf(redm[1][2], redm[1][3])));
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Differential columns: the positive and the negative part of the weights sit
-// on two columns, each with its own non-negative current, its own noise draw
-// and its own UNIPOLAR ADC; the two codes are subtracted digitally.
-//   wq+ = max(wq, 0)   wq- = max(-wq, 0)     f+- = f(|w_raw|) by sign(w_raw)
-//   p+- = sum x * wq+-                       s+- = max(sum x * f+-, 0)
-//   v+- = p+- + eps+- * sqrt(factor * s+-)
-//   q+- = step * clamp(rint(v+- * inv_step), 0, Qu)
-//   out = sum_b (q+ - q-) + bias
-// The split happens once per staged element, from the one wq and the one
-// w_raw load, into four weight tiles (wq+, wq-, f+, f-): LDS is (64 + 4*64)
-// rows, + 64 for |w_raw| (telemetry with abs2). Splitting the loaded
-// fragments in registers instead would repeat the work in every wave and for
-// every k-step fragment, and gfx950 has no packed bf16 max. The positive
-// column of block b keeps the counter (b*M + m)*K + k, the negative column
-// uses ((nblocks + b)*M + m)*K + k: with weights >= 0 and the ADC off this
-// kernel draws and returns what xbar_fwd_kernel returns. Bias is a run-time
-// branch here (bias == nullptr) to halve the instantiation count.
-// ---------------------------------------------------------------------------
-
-template <typename T, int SIGMA_MODE, bool TELEM>
-DEV_INLINE void xbar_diff_store_tiles(char* a_lds, char* bp_lds, char* bn_lds,
-                                      char* cp_lds, char* cn_lds, char* d_lds,
-                                      const XbarRegs<T>& rg) {
-  int row = threadIdx.x >> 2;
-  int seg = threadIdx.x & 3;
-  xbar_put8<T>(a_lds, row, seg, rg.x);
-  float p[8], n[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float q = to_f32(rg.q[j]);
-    p[j] = fmaxf(q, 0.0f);
-    n[j] = fmaxf(-q, 0.0f);
-  }
-  Mma<T>::store8(bp_lds, row, seg * 8, p);
-  Mma<T>::store8(bn_lds, row, seg * 8, n);
-  if (SIGMA_MODE > 0) {
-    float a[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float w = to_f32(rg.w[j]);
-      a[j] = fabsf(w);
-      float v = (SIGMA_MODE == 2) ? a[j] * a[j] + a[j] : a[j];
-      p[j] = (w > 0.0f) ? v : 0.0f;
-      n[j] = (w < 0.0f) ? v : 0.0f;
-    }
-    Mma<T>::store8(cp_lds, row, seg * 8, p);
-    Mma<T>::store8(cn_lds, row, seg * 8, n);
-    if (TELEM && SIGMA_MODE == 2) Mma<T>::store8(d_lds, row, seg * 8, a);
-  }
-}
-
-// TELEM as in xbar_fwd_kernel, per column: telem[1] sums
-// |sum_b (noise+ - noise-)|, sat_count counts column partials with
-// rint(v / step) > Qu or < 0, telem[4] is the max |v+-|; qu = 2^bits - 1
-template <typename T, int SIGMA_MODE, bool ADC, bool TELEM>
-__global__ __launch_bounds__(kBlock)
-void xbar_diff_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
-                          const T* __restrict__ wraw,
-                          const float* __restrict__ bias, T* __restrict__ out,
-                          ConvGeom g, int wpitch, int xbar_rows,
-                          const float* __restrict__ factor_p,
-                          const float* __restrict__ adc_p /* step, 1/step */,
-                          float qu, uint64_t seed, float* __restrict__ telem,
-                          unsigned long long* __restrict__ sat_count,
-                          const int64_t* __restrict__ seed_base) {
-  seed = graph_seed(seed_base, seed);
-  const float factor = (SIGMA_MODE > 0) ? factor_p[0] : 0.0f;
-  const float step = ADC ? adc_p[0] : 1.0f;
-  const float inv_step = ADC ? adc_p[1] : 1.0f;
-  int n0 = blockIdx.x * BN;
-  int64_t m0 = (int64_t)blockIdx.y * BM;
-
-  constexpr int STR = Mma<T>::STRIDE;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* a_lds = smem;                          // BM rows (x)
-  char* bp_lds = smem + BM * STR;              // BN rows (wq+)
-  char* bn_lds = smem + (BM + BN) * STR;       // BN rows (wq-)
-  char* cp_lds = smem + (BM + 2 * BN) * STR;   // BN rows (f+)
-  char* cn_lds = smem + (BM + 3 * BN) * STR;   // BN rows (f-)
-  char* d_lds = smem + (BM + 4 * BN) * STR;    // BN rows (|w_raw|, telem)
-
-  int wid = threadIdx.x / WAVE;
-  int wm = wid >> 1, wn = wid & 1;
-  int lane = threadIdx.x & (WAVE - 1);
-
-  XbarRow xr;
-  {
-    int64_t sm = m0 + (threadIdx.x >> 2);
-    xr.live = sm < g.M;
-    int oh = 0, ow = 0;
-    xr.img = 0;
-    if (xr.live) {
-      int64_t t = sm;
-      ow = (int)(t % g.OW); t /= g.OW;
-      oh = (int)(t % g.OH); t /= g.OH;
-      xr.img = (int)t;
-    }
-    xr.ih0 = oh * g.stride - g.pad;
-    xr.iw0 = ow * g.stride - g.pad;
-    xr.r = xr.s = xr.c = 0;
-    xbar_row_advance(xr, g, (threadIdx.x & 3) * 8);
-  }
-
-  f32x4 accp[2][2] = {}, accn[2][2] = {};     // p+, p-
-  f32x4 saccp[2][2] = {}, saccn[2][2] = {};   // s+, s-
-  f32x4 tacc[2][2] = {};    // sigma_abs of the block (telemetry, abs2)
-  f32x4 oacc[2][2] = {};    // sum_b (q+ - q-)
-  f32x4 ycl[2][2] = {};     // sum_b (p+ - p-) (telemetry)
-  f32x4 ntot[2][2] = {};    // sum_b (noise+ - noise-) (telemetry)
-  float t_sum_sigma = 0.0f, t_sat = 0.0f, t_vmax = 0.0f;
-
-  const int nrows = g.R * g.S * g.C;
-  const int nblocks = (nrows + xbar_rows - 1) / xbar_rows;
-  const int steps_per_block = xbar_rows / BK;
-  int steps_left = steps_per_block;
-  int b = 0;
-  XbarRegs<T> rg;
-  xbar_load_x(rg.x, x, g, xr);
-  xbar_load_w<T, SIGMA_MODE>(rg.q, rg.w, wq, wraw, g.K, n0, 0, nrows, wpitch);
-  for (int ck = 0; ck < nrows; ck += BK) {
-    xbar_diff_store_tiles<T, SIGMA_MODE, TELEM>(a_lds, bp_lds, bn_lds, cp_lds,
-                                                cn_lds, d_lds, rg);
-    __syncthreads();
-    if (ck + BK < nrows) {  // next step's loads, in flight under the MFMAs
-      xbar_row_advance(xr, g, BK);
-      xbar_load_x(rg.x, x, g, xr);
-      xbar_load_w<T, SIGMA_MODE>(rg.q, rg.w, wq, wraw, g.K, n0, ck + BK,
-                                 nrows, wpitch);
-    }
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-      auto a = Mma<T>::load(a_lds, wm * 32 + fm * 16 + (lane & 15), lane);
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-        int brow = wn * 32 + fn * 16 + (lane & 15);
-        auto bqp = Mma<T>::load(bp_lds, brow, lane);
-        Mma<T>::mma(a, bqp, accp[fm][fn]);
-        auto bqn = Mma<T>::load(bn_lds, brow, lane);
-        Mma<T>::mma(a, bqn, accn[fm][fn]);
-        if (SIGMA_MODE > 0) {
-          auto bsp = Mma<T>::load(cp_lds, brow, lane);
-          Mma<T>::mma(a, bsp, saccp[fm][fn]);
-          auto bsn = Mma<T>::load(cn_lds, brow, lane);
-          Mma<T>::mma(a, bsn, saccn[fm][fn]);
-        }
-        if (TELEM && SIGMA_MODE == 2) {
-          auto bt = Mma<T>::load(d_lds, brow, lane);
-          Mma<T>::mma(a, bt, tacc[fm][fn]);
-        }
-      }
-    }
-    __syncthreads();
-
-    if (--steps_left > 0 && ck + BK < nrows) continue;
-    // block boundary (or the end): noise + ADC on both columns' fragments
-    steps_left = steps_per_block;
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-        int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
-        int n = n0 + wn * 32 + fn * 16 + (lane & 15);
-        float gp[4], gn[4];
-        if (SIGMA_MODE > 0) {
-          gauss4(seed, (uint64_t)(((int64_t)b * g.M + mb) * g.K + n), gp);
-          gauss4(seed,
-                 (uint64_t)(((int64_t)(nblocks + b) * g.M + mb) * g.K + n), gn);
-        }
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          bool inside = mb + reg < g.M && n < g.K;
-          float pp = accp[fm][fn][reg], pn = accn[fm][fn][reg];
-          float vp = pp, vn = pn;
-          if (SIGMA_MODE > 0) {
-            float sp = fmaxf(saccp[fm][fn][reg], 0.0f);
-            float sn = fmaxf(saccn[fm][fn][reg], 0.0f);
-            float noisep = gp[reg] * sqrtf(factor * sp);
-            float noisen = gn[reg] * sqrtf(factor * sn);
-            vp = pp + noisep;
-            vn = pn + noisen;
-            if (TELEM) {
-              ntot[fm][fn][reg] += noisep - noisen;
-              if (inside)
-                t_sum_sigma += (SIGMA_MODE == 2)
-                                   ? tacc[fm][fn][reg]
-                                   : saccp[fm][fn][reg] + saccn[fm][fn][reg];
-            }
-          }
-          float qp = vp, qn = vn;
-          if (ADC) {
-            float tp = rintf(vp * inv_step);
-            float tn = rintf(vn * inv_step);
-            if (TELEM && inside) {
-              if (tp > qu || tp < 0.0f) t_sat += 1.0f;
-              if (tn > qu || tn < 0.0f) t_sat += 1.0f;
-            }
-            qp = step * fminf(fmaxf(tp, 0.0f), qu);
-            qn = step * fminf(fmaxf(tn, 0.0f), qu);
-          }
-          if (TELEM) {
-            ycl[fm][fn][reg] += pp - pn;
-            if (inside)
-              t_vmax = fmaxf(t_vmax, fmaxf(fabsf(vp), fabsf(vn)));
-          }
-          oacc[fm][fn][reg] += qp - qn;
-        }
-        accp[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        accn[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        saccp[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        saccn[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        tacc[fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      }
-    }
-    ++b;
-  }
-
-  // bias, the one rounding to the dtype, stores
-  float t_sum_noise = 0.0f, t_max_y = -INFINITY;
-#pragma unroll
-  for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-      int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
-      int n = n0 + wn * 32 + fn * 16 + (lane & 15);
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        int64_t m = mb + reg;
-        if (m < g.M && n < g.K) {
-          float bv = bias ? bias[n] : 0.0f;
-          out[m * g.K + n] = from_f32<T>(oacc[fm][fn][reg] + bv);
-          if (TELEM) {
-            t_sum_noise += fabsf(ntot[fm][fn][reg]);
-            t_max_y = fmaxf(t_max_y, ycl[fm][fn][reg] + bv);
-          }
-        }
-      }
-    }
-  }
-  if (TELEM) {
-    __shared__ float red[4];
-    __shared__ float redm[2][4];
-    float s0 = block_sum(t_sum_sigma, red);
-    __syncthreads();
-    float s1 = block_sum(t_sum_noise, red);
-    __syncthreads();
-    float s3 = block_sum(t_sat, red);  // <= 8192 per epilogue: exact
-    float my = wave_max(t_max_y);
-    float mv = wave_max(t_vmax);
-    if (lane == 0) {
-      redm[0][wid] = my;
-      redm[1][wid] = mv;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      if (SIGMA_MODE > 0) {
-        atomicAdd(&telem[0], s0);
-        atomicAdd(&telem[1], s1);
-      }
-      atomic_max_f32(&telem[2], fmaxf(fmaxf(redm[0][0], redm[0][1]),
-                                      fmaxf(redm[0][2], redm[0][3])));
-      if (ADC) atomicAdd(sat_count, (unsigned long long)(s3 + 0.5f));
-      atomic_max_f32(&telem[4], fmaxf(fmaxf(redm[1][0], redm[1][1]),
-                                      fmaxf(redm[1][2], redm[1][3])));
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Bit-serial inputs: the activation is a B-bit code on the grid x_step and
-// reaches the rows D bits per cycle, J = ceil(B / D) cycles ("slices"). Every
-// slice of every block has its own column current, noise draw and ADC
-// conversion; the digital side shift-adds the slices.
-//   code = clamp(rint(f32(x) * inv_x_step), 0, 2^B - 1)
-//   d_j  = (code >> j*D) & (2^D - 1)                       j = 0..J-1
-//   p_bj = x_step * sum d_j * wq    s_bj = max(x_step * sum d_j * f(|w_raw|), 0)
-//   v_bj = p_bj + eps_bj * sqrt(factor * s_bj)
-//   q_bj = step * clamp(rint(v_bj * inv_step), -Qm, Qm)
-//   out  = sum_b sum_j 2^(jD) * q_bj + bias      (b ascending, j inside b)
-// The MFMA operands are the integers d_j (exact in every dtype); x_step
-// multiplies the fp32 accumulators in the epilogue. The staging thread derives
-// the code once from its 8 activations and writes J activation tiles; the wq
-// and f(|w_raw|) tiles are staged once per k-step and serve every slice, so a
-// k-step costs J x the MFMAs of xbar_fwd_kernel but the same global loads and
-// weight staging. Each slice has p and s accumulator fragments of its own; J
-// is a template parameter so that they stay in registers. The Philox counter
-// of a four-row group is ((b*J + j)*M + m)*K + k: with J = 1 this kernel
-// draws what xbar_fwd_kernel draws. Bias is a run-time branch.
-// ---------------------------------------------------------------------------
-
-// TELEM: telem[5] = sum_bj 2^(jD) sigma_abs_bj, sum |sum_bj 2^(jD) noise_bj|,
-//        max clean shift-added y, (unused, see sat_count), max |v_bj|;
-//        sat_count = number of (b, j) partials with |rint(v_bj / step)| > Qm
-template <typename T, int J, int SIGMA_MODE, bool ADC, bool TELEM>
-__global__ __launch_bounds__(kBlock)
-void xbar_serial_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
-                            const T* __restrict__ wraw,
-                            const float* __restrict__ bias,
-                            T* __restrict__ out, ConvGeom g, int wpitch,
-                            int xbar_rows, int in_bits, int dac_bits,
-                            const float* __restrict__ dac_p /* x_step, 1/x_step */,
-                            const float* __restrict__ factor_p,
-                            const float* __restrict__ adc_p /* step, 1/step */,
-                            float qm, uint64_t seed, float* __restrict__ telem,
-                            unsigned long long* __restrict__ sat_count,
-                            const int64_t* __restrict__ seed_base) {
-  seed = graph_seed(seed_base, seed);
-  const float factor = (SIGMA_MODE > 0) ? factor_p[0] : 0.0f;
-  const float step = ADC ? adc_p[0] : 1.0f;
-  const float inv_step = ADC ? adc_p[1] : 1.0f;
-  const float x_step = dac_p[0];
-  const float inv_x_step = dac_p[1];
-  const float code_max = (float)((1 << in_bits) - 1);
-  const int dmask = (1 << dac_bits) - 1;
-  int n0 = blockIdx.x * BN;
-  int64_t m0 = (int64_t)blockIdx.y * BM;
-
-  constexpr int STR = Mma<T>::STRIDE;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* a_lds = smem;                              // J x BM rows (d_j)
-  char* b_lds = smem + J * BM * STR;               // BN rows (wq)
-  char* c_lds = smem + (J * BM + BN) * STR;        // BN rows (f(|w_raw|))
-  char* d_lds = smem + (J * BM + 2 * BN) * STR;    // BN rows (|w_raw|, telem)
-
-  int wid = threadIdx.x / WAVE;
-  int wm = wid >> 1, wn = wid & 1;
-  int lane = threadIdx.x & (WAVE - 1);
-
-  XbarRow xr;
-  {
-    int64_t sm = m0 + (threadIdx.x >> 2);
-    xr.live = sm < g.M;
-    int oh = 0, ow = 0;
-    xr.img = 0;
-    if (xr.live) {
-      int64_t t = sm;
-      ow = (int)(t % g.OW); t /= g.OW;
-      oh = (int)(t % g.OH); t /= g.OH;
-      xr.img = (int)t;
-    }
-    xr.ih0 = oh * g.stride - g.pad;
-    xr.iw0 = ow * g.stride - g.pad;
-    xr.r = xr.s = xr.c = 0;
-    xbar_row_advance(xr, g, (threadIdx.x & 3) * 8);
-  }
-
-  f32x4 acc[J][2][2] = {};    // sum d_j * wq of the block
-  f32x4 sacc[J][2][2] = {};   // sum d_j * f(|w_raw|) of the block
-  f32x4 tacc[J][2][2] = {};   // sum d_j * |w_raw| (telemetry, abs2)
-  f32x4 oacc[2][2] = {};      // sum_bj 2^(jD) q_bj
-  f32x4 ycl[2][2] = {};       // sum_bj 2^(jD) p_bj (telemetry)
-  f32x4 ntot[2][2] = {};      // sum_bj 2^(jD) noise_bj (telemetry)
-  float t_sum_sigma = 0.0f, t_sat = 0.0f, t_vmax = 0.0f;
-
-  const int nrows = g.R * g.S * g.C;
-  const int steps_per_block = xbar_rows / BK;
-  int steps_left = steps_per_block;
-  int b = 0;
-  XbarRegs<T> rg;
-  xbar_load_x(rg.x, x, g, xr);
-  xbar_load_w<T, SIGMA_MODE>(rg.q, rg.w, wq, wraw, g.K, n0, 0, nrows, wpitch);
-  for (int ck = 0; ck < nrows; ck += BK) {
-    {
-      // the code, once; then one activation tile per slice
-      int row = threadIdx.x >> 2;
-      int seg = threadIdx.x & 3;
-      int code[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float c = rintf(to_f32(rg.x[e]) * inv_x_step);
-        code[e] = (int)fminf(fmaxf(c, 0.0f), code_max);
-      }
-#pragma unroll
-      for (int j = 0; j < J; ++j) {
-        float d[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          d[e] = (float)((code[e] >> (j * dac_bits)) & dmask);
-        Mma<T>::store8(a_lds + j * BM * STR, row, seg * 8, d);
-      }
-      xbar_put8<T>(b_lds, row, seg, rg.q);
-      if (SIGMA_MODE > 0) {
-        float a[8], v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          a[e] = fabsf(to_f32(rg.w[e]));
-          v[e] = (SIGMA_MODE == 2) ? a[e] * a[e] + a[e] : a[e];
-        }
-        Mma<T>::store8(c_lds, row, seg * 8, v);
-        if (TELEM && SIGMA_MODE == 2) Mma<T>::store8(d_lds, row, seg * 8, a);
-      }
-    }
-    __syncthreads();
-    if (ck + BK < nrows) {  // next step's loads, in flight under the MFMAs
-      xbar_row_advance(xr, g, BK);
-      xbar_load_x(rg.x, x, g, xr);
-      xbar_load_w<T, SIGMA_MODE>(rg.q, rg.w, wq, wraw, g.K, n0, ck + BK,
-                                 nrows, wpitch);
-    }
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-      typename Mma<T>::frag a[J];
-#pragma unroll
-      for (int j = 0; j < J; ++j)
-        a[j] = Mma<T>::load(a_lds + j * BM * STR,
-                            wm * 32 + fm * 16 + (lane & 15), lane);
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-        int brow = wn * 32 + fn * 16 + (lane & 15);
-        auto bq = Mma<T>::load(b_lds, brow, lane);
-#pragma unroll
-        for (int j = 0; j < J; ++j) Mma<T>::mma(a[j], bq, acc[j][fm][fn]);
-        if (SIGMA_MODE > 0) {
-          auto bs = Mma<T>::load(c_lds, brow, lane);
-#pragma unroll
-          for (int j = 0; j < J; ++j) Mma<T>::mma(a[j], bs, sacc[j][fm][fn]);
-        }
-        if (TELEM && SIGMA_MODE == 2) {
-          auto bt = Mma<T>::load(d_lds, brow, lane);
-#pragma unroll
-          for (int j = 0; j < J; ++j) Mma<T>::mma(a[j], bt, tacc[j][fm][fn]);
-        }
-      }
-    }
-    __syncthreads();
-
-    if (--steps_left > 0 && ck + BK < nrows) continue;
-    // block boundary (or the end): J noise draws and J ADCs on the live
-    // fragments, shift-added into the output
-    steps_left = steps_per_block;
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-        int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
-        int n = n0 + wn * 32 + fn * 16 + (lane & 15);
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-          const float shift = (float)(1 << (j * dac_bits));
-          float g4[4];
-          if (SIGMA_MODE > 0)
-            gauss4(seed,
-                   (uint64_t)((((int64_t)b * J + j) * g.M + mb) * g.K + n),
-                   g4);
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) {
-            bool inside = mb + reg < g.M && n < g.K;
-            float p = __fmul_rn(x_step, acc[j][fm][fn][reg]);
-            float v = p;
-            if (SIGMA_MODE > 0) {
-              float sig = fmaxf(__fmul_rn(x_step, sacc[j][fm][fn][reg]), 0.0f);
-              float noise = g4[reg] * sqrtf(factor * sig);
-              v = p + noise;
-              if (TELEM) {
-                ntot[fm][fn][reg] += shift * noise;
-                if (inside)
-                  t_sum_sigma += shift * x_step
-                      * ((SIGMA_MODE == 2) ? tacc[j][fm][fn][reg]
-                                           : sacc[j][fm][fn][reg]);
-              }
-            }
-            float q = v;
-            if (ADC) {
-              float t = rintf(v * inv_step);
-              if (TELEM && inside && fabsf(t) > qm) t_sat += 1.0f;
-              q = step * fminf(fmaxf(t, -qm), qm);
-            }
-            if (TELEM) {
-              ycl[fm][fn][reg] += shift * p;
-              if (inside) t_vmax = fmaxf(t_vmax, fabsf(v));
-            }
-            oacc[fm][fn][reg] += shift * q;
-          }
-          acc[j][fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-          sacc[j][fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-          tacc[j][fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        }
-      }
-    }
-    ++b;
-  }
-
-  // bias, the one rounding to the dtype, stores
-  float t_sum_noise = 0.0f, t_max_y = -INFINITY;
-#pragma unroll
-  for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-      int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
-      int n = n0 + wn * 32 + fn * 16 + (lane & 15);
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        int64_t m = mb + reg;
-        if (m < g.M && n < g.K) {
-          float bv = bias ? bias[n] : 0.0f;
-          out[m * g.K + n] = from_f32<T>(oacc[fm][fn][reg] + bv);
-          if (TELEM) {
-            t_sum_noise += fabsf(ntot[fm][fn][reg]);
-            t_max_y = fmaxf(t_max_y, ycl[fm][fn][reg] + bv);
-          }
-        }
-      }
-    }
-  }
-  if (TELEM) {
-    __shared__ float red[4];
-    __shared__ float redm[2][4];
-    float s0 = block_sum(t_sum_sigma, red);
-    __syncthreads();
-    float s1 = block_sum(t_sum_noise, red);
-    __syncthreads();
-    float s3 = block_sum(t_sat, red);  // <= J * nblocks * 4096: exact
-    float my = wave_max(t_max_y);
-    float mv = wave_max(t_vmax);
-    if (lane == 0) {
-      redm[0][wid] = my;
-      redm[1][wid] = mv;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      if (SIGMA_MODE > 0) {
-        atomicAdd(&telem[0], s0);
-        atomicAdd(&telem[1], s1);
-      }
-      atomic_max_f32(&telem[2], fmaxf(fmaxf(redm[0][0], redm[0][1]),
-                                      fmaxf(redm[0][2], redm[0][3])));
-      if (ADC) atomicAdd(sat_count, (unsigned long long)(s3 + 0.5f));
-      atomic_max_f32(&telem[4], fmaxf(fmaxf(redm[1][0], redm[1][1]),
-                                      fmaxf(redm[1][2], redm[1][3])));
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Bit-sliced weights: a cell holds E bits, so the B-bit weight code (offset
-// binary on the weight quantiser's grid w = w_min + code * w_step) is spread
-// over NSLICE = ceil(B / E) columns. Every column of every block has its own
-// current, noise draw and UNIPOLAR ADC conversion; the digital side shift-adds
-// the columns and adds the offset w_min * sum x.
-//   code = clamp(rint((f32(wq) - w_min) * inv_w_step), 0, 2^B - 1)
-//   d_t  = (code >> t*E) & (2^E - 1)                       t = 0..NSLICE-1
-//   p_bt = w_step * sum x * d_t
-//   s_bt = max(p_bt, 0)                                    (abs: g = w_step d)
-//        = max(w_step^2 * sum x * d_t^2 + p_bt, 0)         (abs2: g^2 + g)
-//   v_bt = p_bt + eps_bt * sqrt(factor * s_bt)
-//   q_bt = step * clamp(rint(v_bt * inv_step), 0, Qu)
-//   X_b  = sum x
-//   out  = sum_b (sum_t 2^(tE) q_bt + w_min * X_b) + bias
-// (b ascending, t ascending inside b, the offset after the block's columns).
-// The MFMA operands are the activation and the integers d_t, d_t^2 <= 225
-// (exact in every dtype); w_step and w_step^2 multiply the fp32 accumulators
-// in the epilogue, so abs mode needs no sigma MFMA at all; neither does abs2
-// with one-bit cells, where d_t^2 = d_t: the host then launches the abs
-// instantiation with ``fold_squares`` set and the epilogue adds
-// w_step^2 * sum x * d_t from the one accumulator. The staging thread
-// derives the code once from its 8 wq elements and writes NSLICE digit tiles
-// (and NSLICE tiles of d_t^2 with abs2); the activation tile is staged once
-// per k-step and serves every column. X_b is one MFMA per fm against an
-// all-ones B fragment held in registers: every column of the result is the
-// row sum, so it serves both fn. w_raw is not read: the conductances are the
-// digits. The Philox counter of a four-row group is
-// ((b*NSLICE + t)*M + m)*K + k: with one slice, w_step 1 and w_min 0 this
-// kernel draws what xbar_fwd_kernel draws. Bias is a run-time branch.
-// ---------------------------------------------------------------------------
-
-// TELEM: telem[5] = sum_bt p_bt (the current the cells draw, NOT
-//        shift-weighted), sum |sum_bt 2^(tE) noise_bt|, max clean shift-added
-//        y with the offset and the bias, (unused, see sat_count), max |v_bt|;
-//        sat_count = number of (b, t) partials with rint(v_bt / step) > Qu
-//        or < 0
-//
-// PROG ("programmed cells"): the conductances are DATA, not digits. ``cells``
-// is G[NSLICE][K][wpitch] in digit units, written once per layer by
-// xbar_program_cells_kernel (device-to-device variation, stuck-at cells):
-//   p_bt = w_step * sum x * G_t
-//   s_bt = max(p_bt, 0)                                                (abs)
-//        = max(w_step^2 * sum x * round_to_dtype(f32(G_t)^2) + p_bt, 0) (abs2)
-// and everything from v_bt on is the model above. The staging thread loads
-// its 8-span of each of the NSLICE slices of G (in flight under the MFMAs,
-// as the wq span is), stores them as the conductance tiles and, with abs2,
-// their squares (fp32, rounded once). wq is not read; spans past K or past
-// the contraction are zeros. G^2 != G, so ``fold_squares`` is never set.
-template <typename T, int NSLICE, int SIGMA_MODE, bool ADC, bool TELEM,
-          bool PROG>
-__global__ __launch_bounds__(kBlock)
-void xbar_cells_fwd_kernel(const T* __restrict__ x, const T* __restrict__ wq,
-                           const float* __restrict__ bias,
-                           T* __restrict__ out, ConvGeom g, int wpitch,
-                           int xbar_rows, int w_bits, int cell_bits,
-                           int fold_squares /* abs2 on one-bit cells */,
-                           const float* __restrict__ cell_p /* w_step, 1/w_step, w_min */,
-                           const float* __restrict__ factor_p,
-                           const float* __restrict__ adc_p /* step, 1/step */,
-                           float qu, uint64_t seed, float* __restrict__ telem,
-                           unsigned long long* __restrict__ sat_count,
-                           const int64_t* __restrict__ seed_base,
-                           const T* __restrict__ cells /* PROG: G */,
-                           int64_t cell_stride /* K * wpitch */) {
-  seed = graph_seed(seed_base, seed);
-  const float factor = (SIGMA_MODE > 0) ? factor_p[0] : 0.0f;
-  const float step = ADC ? adc_p[0] : 1.0f;
-  const float inv_step = ADC ? adc_p[1] : 1.0f;
-  const float w_step = cell_p[0];
-  const float inv_w_step = cell_p[1];
-  const float w_min = cell_p[2];
-  const float w_step2 = __fmul_rn(w_step, w_step);
-  // SIGMA_MODE 1: s = sq1 * sum x * d_t + p_bt with sq1 = 0 (abs, s = p_bt
-  // exactly) or w_step^2 (abs2 on one-bit cells)
-  const float sq1 = fold_squares ? w_step2 : 0.0f;
-  const float code_max = (float)((1 << w_bits) - 1);
-  const int dmask = (1 << cell_bits) - 1;
-  int n0 = blockIdx.x * BN;
-  int64_t m0 = (int64_t)blockIdx.y * BM;
-
-  constexpr int STR = Mma<T>::STRIDE;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* a_lds = smem;                               // BM rows (x)
-  char* d_lds = smem + BM * STR;                    // NSLICE x BN rows (d_t)
-  char* e_lds = smem + (BM + NSLICE * BN) * STR;    // NSLICE x BN rows (d_t^2)
-
-  int wid = threadIdx.x / WAVE;
-  int wm = wid >> 1, wn = wid & 1;
-  int lane = threadIdx.x & (WAVE - 1);
-
-  XbarRow xr;
-  {
-    int64_t sm = m0 + (threadIdx.x >> 2);
-    xr.live = sm < g.M;
-    int oh = 0, ow = 0;
-    xr.img = 0;
-    if (xr.live) {
-      int64_t t = sm;
-      ow = (int)(t % g.OW); t /= g.OW;
-      oh = (int)(t % g.OH); t /= g.OH;
-      xr.img = (int)t;
-    }
-    xr.ih0 = oh * g.stride - g.pad;
-    xr.iw0 = ow * g.stride - g.pad;
-    xr.r = xr.s = xr.c = 0;
-    xbar_row_advance(xr, g, (threadIdx.x & 3) * 8);
-  }
-
-  typename Mma<T>::frag ones;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = 1.0f;
-
-  f32x4 acc[NSLICE][2][2] = {};    // sum x * d_t of the block
-  f32x4 sacc[NSLICE][2][2] = {};   // sum x * d_t^2 of the block (abs2)
-  f32x4 xacc[2] = {};              // X_b = sum x of the block, per fm
-  f32x4 oacc[2][2] = {};           // sum_b (sum_t 2^(tE) q_bt + w_min X_b)
-  f32x4 ycl[2][2] = {};            // the same with p_bt for q_bt (telemetry)
-  f32x4 ntot[2][2] = {};           // sum_bt 2^(tE) noise_bt (telemetry)
-  float t_sum_sigma = 0.0f, t_sat = 0.0f, t_vmax = 0.0f;
-
-  const int nrows = g.R * g.S * g.C;
-  const int steps_per_block = xbar_rows / BK;
-  int steps_left = steps_per_block;
-  int b = 0;
-  XbarRegs<T> rg;   // rg.w stays unused: the conductances are the digits
-  // PROG: the thread's span of every slice of G, in place of rg.q
-  alignas(16) T gq[PROG ? NSLICE : 1][8];
-  xbar_load_x(rg.x, x, g, xr);
-  if (PROG) {
-#pragma unroll
-    for (int t = 0; t < NSLICE; ++t)
-      xbar_load_w<T, 0>(gq[PROG ? t : 0], rg.w, cells + t * cell_stride, cells,
-                        g.K, n0, 0, nrows, wpitch);
-  } else {
-    xbar_load_w<T, 0>(rg.q, rg.w, wq, wq, g.K, n0, 0, nrows, wpitch);
-  }
-  for (int ck = 0; ck < nrows; ck += BK) {
-    if (PROG) {
-      // the conductance tiles as they are; squares in fp32, rounded once
-      int row = threadIdx.x >> 2;
-      int seg = threadIdx.x & 3;
-      xbar_put8<T>(a_lds, row, seg, rg.x);
-#pragma unroll
-      for (int t = 0; t < NSLICE; ++t) {
-        xbar_put8<T>(d_lds + t * BN * STR, row, seg, gq[PROG ? t : 0]);
-        if (SIGMA_MODE == 2) {
-          float d[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            float gv = to_f32(gq[PROG ? t : 0][e]);
-            d[e] = __fmul_rn(gv, gv);
-          }
-          Mma<T>::store8(e_lds + t * BN * STR, row, seg * 8, d);
-        }
-      }
-    } else {
-      // the code, once; then one digit tile (and one of squares) per slice.
-      // Rows past the contraction or past K stage the code of a zero weight:
-      // their activations are zero / their outputs are never stored
-      int row = threadIdx.x >> 2;
-      int seg = threadIdx.x & 3;
-      xbar_put8<T>(a_lds, row, seg, rg.x);
-      int code[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float c = rintf((to_f32(rg.q[e]) - w_min) * inv_w_step);
-        code[e] = (int)fminf(fmaxf(c, 0.0f), code_max);
-      }
-#pragma unroll
-      for (int t = 0; t < NSLICE; ++t) {
-        float d[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          d[e] = (float)((code[e] >> (t * cell_bits)) & dmask);
-        Mma<T>::store8(d_lds + t * BN * STR, row, seg * 8, d);
-        if (SIGMA_MODE == 2) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) d[e] *= d[e];
-          Mma<T>::store8(e_lds + t * BN * STR, row, seg * 8, d);
-        }
-      }
-    }
-    __syncthreads();
-    if (ck + BK < nrows) {  // next step's loads, in flight under the MFMAs
-      xbar_row_advance(xr, g, BK);
-      xbar_load_x(rg.x, x, g, xr);
-      if (PROG) {
-#pragma unroll
-        for (int t = 0; t < NSLICE; ++t)
-          xbar_load_w<T, 0>(gq[PROG ? t : 0], rg.w, cells + t * cell_stride,
-                            cells, g.K, n0, ck + BK, nrows, wpitch);
-      } else {
-        xbar_load_w<T, 0>(rg.q, rg.w, wq, wq, g.K, n0, ck + BK, nrows, wpitch);
-      }
-    }
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-      auto a = Mma<T>::load(a_lds, wm * 32 + fm * 16 + (lane & 15), lane);
-      Mma<T>::mma(a, ones, xacc[fm]);
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-        int brow = wn * 32 + fn * 16 + (lane & 15);
-#pragma unroll
-        for (int t = 0; t < NSLICE; ++t) {
-          auto bd = Mma<T>::load(d_lds + t * BN * STR, brow, lane);
-          Mma<T>::mma(a, bd, acc[t][fm][fn]);
-          if (SIGMA_MODE == 2) {
-            auto be = Mma<T>::load(e_lds + t * BN * STR, brow, lane);
-            Mma<T>::mma(a, be, sacc[t][fm][fn]);
-          }
-        }
-      }
-    }
-    __syncthreads();
-
-    if (--steps_left > 0 && ck + BK < nrows) continue;
-    // block boundary (or the end): NSLICE noise draws and NSLICE unipolar
-    // ADCs on the live fragments, shift-added; then the block's offset
-    steps_left = steps_per_block;
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-        int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
-        int n = n0 + wn * 32 + fn * 16 + (lane & 15);
-#pragma unroll
-        for (int t = 0; t < NSLICE; ++t) {
-          const float shift = (float)(1 << (t * cell_bits));
-          float g4[4];
-          if (SIGMA_MODE > 0)
-            gauss4(seed,
-                   (uint64_t)((((int64_t)b * NSLICE + t) * g.M + mb) * g.K + n),
-                   g4);
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) {
-            bool inside = mb + reg < g.M && n < g.K;
-            float p = __fmul_rn(w_step, acc[t][fm][fn][reg]);
-            float v = p;
-            if (SIGMA_MODE > 0) {
-              float sig = (SIGMA_MODE == 2)
-                  ? __fadd_rn(__fmul_rn(w_step2, sacc[t][fm][fn][reg]), p)
-                  : __fadd_rn(__fmul_rn(sq1, acc[t][fm][fn][reg]), p);
-              sig = fmaxf(sig, 0.0f);
-              float noise = g4[reg] * sqrtf(factor * sig);
-              v = p + noise;
-              if (TELEM) {
-                ntot[fm][fn][reg] += shift * noise;
-                if (inside) t_sum_sigma += p;
-              }
-            }
-            float q = v;
-            if (ADC) {
-              float c = rintf(v * inv_step);
-              if (TELEM && inside && (c > qu || c < 0.0f)) t_sat += 1.0f;
-              q = step * fminf(fmaxf(c, 0.0f), qu);
-            }
-            if (TELEM) {
-              ycl[fm][fn][reg] += shift * p;
-              if (inside) t_vmax = fmaxf(t_vmax, fabsf(v));
-            }
-            oacc[fm][fn][reg] += shift * q;
-          }
-          acc[t][fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-          sacc[t][fm][fn] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        }
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          float off = __fmul_rn(w_min, xacc[fm][reg]);
-          oacc[fm][fn][reg] = __fadd_rn(oacc[fm][fn][reg], off);
-          if (TELEM) ycl[fm][fn][reg] = __fadd_rn(ycl[fm][fn][reg], off);
-        }
-      }
-      xacc[fm] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
-    ++b;
-  }
-
-  // bias, the one rounding to the dtype, stores
-  float t_sum_noise = 0.0f, t_max_y = -INFINITY;
-#pragma unroll
-  for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-      int64_t mb = m0 + wm * 32 + fm * 16 + 4 * (lane >> 4);
-      int n = n0 + wn * 32 + fn * 16 + (lane & 15);
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        int64_t m = mb + reg;
-        if (m < g.M && n < g.K) {
-          float bv = bias ? bias[n] : 0.0f;
-          out[m * g.K + n] = from_f32<T>(oacc[fm][fn][reg] + bv);
-          if (TELEM) {
-            t_sum_noise += fabsf(ntot[fm][fn][reg]);
-            t_max_y = fmaxf(t_max_y, ycl[fm][fn][reg] + bv);
-          }
-        }
-      }
-    }
-  }
-  if (TELEM) {
-    __shared__ float red[4];
-    __shared__ float redm[2][4];
-    float s0 = block_sum(t_sum_sigma, red);
-    __syncthreads();
-    float s1 = block_sum(t_sum_noise, red);
-    __syncthreads();
-    float s3 = block_sum(t_sat, red);  // <= NSLICE * nblocks * 4096: exact
-    float my = wave_max(t_max_y);
-    float mv = wave_max(t_vmax);
-    if (lane == 0) {
-      redm[0][wid] = my;
-      redm[1][wid] = mv;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      if (SIGMA_MODE > 0) {
-        atomicAdd(&telem[0], s0);
-        atomicAdd(&telem[1], s1);
-      }
-      atomic_max_f32(&telem[2], fmaxf(fmaxf(redm[0][0], redm[0][1]),
-                                      fmaxf(redm[0][2], redm[0][3])));
-      if (ADC) atomicAdd(sat_count, (unsigned long long)(s3 + 0.5f));
-      atomic_max_f32(&telem[4], fmaxf(fmaxf(redm[1][0], redm[1][1]),
-                                      fmaxf(redm[1][2], redm[1][3])));
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Programming a layer's weight codes onto imperfect cells: one launch writes
-// G[NSLICE][K][pitch] (digit units, the dtype of wq) for the PROG path above.
-// For the weight matrix in crossbar-row order [K, n], slice t, column k, row i
-//   code   = clamp(rint((f32(wq) - w_min) * inv_w_step), 0, 2^B - 1)
-//   d_t    = (code >> tE) & (2^E - 1)
-//   (u, z) = ONE Philox4x32 draw, key = chip seed, counter = (t*K + k)*n + i:
-//            u = u01(word 0), z = Box-Muller on words 2, 3
-//   d'_t   = 0 if u < p_off (stuck at the high-resistance state),
-//            2^E - 1 else if u < p_off + p_on (stuck on), else d_t
-//   G_t    = round_to_dtype(max(d'_t * (1 + sigma * z), 0))
-// in fp32 with the one rounding. Multiplicative Gaussian variation clamped at
-// zero: an off cell stays off, a stuck-on cell varies like any other.
-// Log-normal variation and additive HRS leakage are not modelled. One thread
-// owns a (k, i) and walks the slices; columns n..pitch-1 are written as zeros.
-// ``fresh`` sends the seed through graph_seed, so a captured step programs a
-// new chip on every replay; a fixed chip keeps the seed as given.
-// ---------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(kBlock)
-void xbar_program_cells_kernel(const T* __restrict__ wq, T* __restrict__ G,
-                               int K, int n, int pitch, int nslice,
-                               int w_bits, int cell_bits,
-                               const float* __restrict__ cell_p,
-                               float sigma, float p_off, float p_on,
-                               uint64_t seed, int fresh,
-                               const int64_t* __restrict__ seed_base) {
-  if (fresh) seed = graph_seed(seed_base, seed);
-  int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (idx >= (int64_t)K * pitch) return;
-  int k = (int)(idx / pitch);
-  int i = (int)(idx - (int64_t)k * pitch);
-  const int64_t slice = (int64_t)K * pitch;
-  if (i >= n) {
-    for (int t = 0; t < nslice; ++t) G[t * slice + idx] = from_f32<T>(0.0f);
-    return;
-  }
-  const float inv_w_step = cell_p[1];
-  const float w_min = cell_p[2];
-  const float code_max = (float)((1 << w_bits) - 1);
-  const int dmask = (1 << cell_bits) - 1;
-  const float p_any = __fadd_rn(p_off, p_on);
-  float c = rintf((to_f32(wq[(int64_t)k * n + i]) - w_min) * inv_w_step);
-  int code = (int)fminf(fmaxf(c, 0.0f), code_max);
-  for (int t = 0; t < nslice; ++t) {
-    Philox4 p = philox4x32(seed, (uint64_t)(((int64_t)t * K + k) * n + i));
-    float u = u01(p.x);
-    float z = sqrtf(-2.0f * __logf(u01_open(p.z)))
-        * __cosf(6.2831853071795864f * u01(p.w));
-    float d = (float)((code >> (t * cell_bits)) & dmask);
-    if (u < p_off) d = 0.0f;
-    else if (u < p_any) d = (float)dmask;
-    float v = __fmul_rn(d, __fadd_rn(1.0f, __fmul_rn(sigma, z)));
-    G[t * slice + idx] = from_f32<T>(fmaxf(v, 0.0f));
-  }
-}
-
-void check_xbar_args(int64_t sigma_mode, int64_t xbar_rows, int64_t adc_bits,
-                     const torch::Tensor& adc, const torch::Tensor& x,
-                     const char* who) {
-  check_sigma_mode(sigma_mode, true, who);
-  TORCH_CHECK(xbar_rows > 0 && xbar_rows % BK == 0, who,
-              ": xbar_rows must be a positive multiple of ", BK, ", got ",
-              xbar_rows);
-  TORCH_CHECK(adc_bits == 0 || (adc_bits >= 2 && adc_bits <= 16), who,
-              ": adc_bits must be 0 or 2..16, got ", adc_bits);
-  TORCH_CHECK(sigma_mode != 0 || adc_bits != 0, who,
-              ": noise (sigma_mode) and ADC (adc_bits) are both off");
-  if (adc_bits > 0)
-    TORCH_CHECK(adc.numel() == 2 && adc.scalar_type() == torch::kFloat32 &&
-                    adc.is_contiguous() && adc.device() == x.device(),
-                who, ": adc must be the fp32 device tensor [step, 1/step]");
-}
-
-// x, wq2, wr2 are raw NHWC / [K, nrows] row-matrix views; out is allocated by
-// the caller with M*K elements in [M, K] raw order
-std::vector<torch::Tensor> xbar_fwd_impl(
-    const torch::Tensor& x, torch::Tensor wq2, torch::Tensor wr2,
-    const torch::Tensor& bias, ConvGeom g, torch::Tensor out,
-    int64_t sigma_mode, const torch::Tensor& factor, int64_t xbar_rows,
-    int64_t adc_bits, const torch::Tensor& adc, int64_t seed, bool telem,
-    bool diff, const char* who) {
-  check_xbar_args(sigma_mode, xbar_rows, adc_bits, adc, x, who);
-  int nrows = g.R * g.S * g.C;
-  TORCH_CHECK(wq2.dim() == 2 && wq2.size(0) == g.K && wq2.size(1) == nrows &&
-                  wr2.sizes() == wq2.sizes(),
-              who, ": weight shape mismatch");
-  TORCH_CHECK(wq2.scalar_type() == x.scalar_type() &&
-                  wr2.scalar_type() == x.scalar_type(),
-              who, ": x and the weights must share one dtype");
-  int pitch = nrows;
-  if (x.element_size() == 2 && (nrows & 7) != 0) {
-    // zero-pad the (small) weight rows so the kernel's 16-byte row loads
-    // are aligned
-    pitch = (nrows + 7) & ~7;
-    bool same = wr2.is_same(wq2);
-    wq2 = at::constant_pad_nd(wq2, {0, pitch - nrows}, 0);
-    wr2 = same ? wq2 : at::constant_pad_nd(wr2, {0, pitch - nrows}, 0);
-  }
-  wq2 = wq2.contiguous();
-  wr2 = wr2.contiguous();
-  bool has_bias = bias.numel() > 0;
-  if (has_bias) TORCH_CHECK(bias.numel() == g.K, who, ": bias size mismatch");
-  torch::Tensor bias_f;
-  if (has_bias) bias_f = bias.to(torch::kFloat32).contiguous();
-  auto f32 = x.options().dtype(torch::kFloat32);
-  torch::Tensor tele, sat;
-  if (telem) {
-    tele = torch::zeros({5}, f32);
-    tele[2] = -std::numeric_limits<float>::infinity();
-    sat = torch::zeros({1}, x.options().dtype(torch::kLong));
-  } else {
-    tele = torch::empty({0}, f32);
-  }
-  auto factor_f = factor.to(torch::kFloat32).reshape({1}).contiguous();
-  bool adc_on = adc_bits > 0;
-  // top ADC code: bipolar +-Qm, or unipolar 0..Qu on differential columns
-  float qm = !adc_on ? 0.0f
-             : diff  ? (float)((1 << adc_bits) - 1)
-                     : (float)((1 << (adc_bits - 1)) - 1);
-  dim3 grid((g.K + BN - 1) / BN, (int)((g.M + BM - 1) / BM));
-  NN_DISPATCH(x.scalar_type(), "xbar_fwd", [&] {
-    using T = typename DevT<scalar_t>::type;
-    size_t lds = (size_t)(BM + (diff ? 5 : 3) * BN) * Mma<T>::STRIDE;
-    auto stream = c10::hip::getCurrentHIPStream();
-    const T* xp = (const T*)x.data_ptr();
-    const T* wqp = (const T*)wq2.data_ptr();
-    const T* wrp = (const T*)wr2.data_ptr();
-    const float* bp = has_bias ? bias_f.data_ptr<float>() : nullptr;
-    T* op = (T*)out.data_ptr();
-    float* tp = telem ? tele.data_ptr<float>() : nullptr;
-    unsigned long long* sp =
-        telem ? (unsigned long long*)sat.data_ptr<int64_t>() : nullptr;
-    const float* f = factor_f.data_ptr<float>();
-    const float* ap = adc_on ? adc.data_ptr<float>() : nullptr;
-    uint64_t sd = (uint64_t)seed;
-    auto launch = [&](auto sm, auto ad, auto tl, auto bi) {
-      hipLaunchKernelGGL((xbar_fwd_kernel<T, decltype(sm)::value,
-                          decltype(ad)::value, decltype(tl)::value,
-                          decltype(bi)::value>), grid, dim3(kBlock), lds,
-                         stream, xp, wqp, wrp, bp, op, g, pitch,
-                         (int)xbar_rows, f, ap, qm, sd, tp, sp, g_seed_base);
-    };
-    using TT = std::true_type; using FF = std::false_type;
-    auto with_bias = [&](auto sm, auto ad, auto tl) {
-      if (has_bias) launch(sm, ad, tl, TT{}); else launch(sm, ad, tl, FF{});
-    };
-    auto launch_diff = [&](auto sm, auto ad, auto tl) {
-      hipLaunchKernelGGL((xbar_diff_fwd_kernel<T, decltype(sm)::value,
-                          decltype(ad)::value, decltype(tl)::value>), grid,
-                         dim3(kBlock), lds, stream, xp, wqp, wrp, bp, op, g,
-                         pitch, (int)xbar_rows, f, ap, qm, sd, tp, sp,
-                         g_seed_base);
-    };
-    auto with_route = [&](auto sm, auto ad, auto tl) {
-      if (diff) launch_diff(sm, ad, tl); else with_bias(sm, ad, tl);
-    };
-    auto with_telem = [&](auto sm, auto ad) {
-      if (telem) with_route(sm, ad, TT{}); else with_route(sm, ad, FF{});
-    };
-    auto with_adc = [&](auto sm) {
-      if (adc_on) with_telem(sm, TT{}); else with_telem(sm, FF{});
-    };
-    // check_xbar_args left exactly these: 0 (ADC on), 1, 2
-    if (sigma_mode == 0) with_telem(std::integral_constant<int, 0>{}, TT{});
-    else if (sigma_mode == 1) with_adc(std::integral_constant<int, 1>{});
-    else with_adc(std::integral_constant<int, 2>{});
-  });
-  HIP_CHECK_LAST();
-  if (telem) tele.narrow(0, 3, 1).copy_(sat);
-  return {out, tele};
-}
-
-std::vector<torch::Tensor> xbar_conv_entry(
-    const torch::Tensor& x, const torch::Tensor& wq, const torch::Tensor& wraw,
-    const torch::Tensor& bias, int64_t stride, int64_t pad, int64_t sigma_mode,
-    const torch::Tensor& factor, int64_t xbar_rows, int64_t adc_bits,
-    const torch::Tensor& adc, int64_t seed, bool telem, bool diff,
-    const char* who) {
-  const std::string name(who);
-  check_cl(x, (name + " x").c_str());
-  check_cl(wq, (name + " wq").c_str());
-  check_cl(wraw, (name + " wraw").c_str());
-  TORCH_CHECK(wq.size(1) == x.size(1), who, ": channel mismatch");
-  auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
-                     (int)x.size(1), (int)wq.size(0), (int)wq.size(2),
-                     (int)wq.size(3), (int)stride, (int)pad);
-  TORCH_CHECK(g.OH > 0 && g.OW > 0, who, ": empty output");
-  auto out = torch::empty({g.N, g.K, g.OH, g.OW},
-                          x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  int64_t nrows = (int64_t)g.R * g.S * g.C;
-  // channels_last [K, C, R, S] is the raw [K, (r, s, c)] row matrix
-  auto rows = [&](const torch::Tensor& w) {
-    return w.permute({0, 2, 3, 1}).reshape({(int64_t)g.K, nrows});
-  };
-  auto wq2 = rows(wq);
-  auto wr2 = wraw.is_same(wq) ? wq2 : rows(wraw);
-  return xbar_fwd_impl(x, wq2, wr2, bias, g, out, sigma_mode, factor,
-                       xbar_rows, adc_bits, adc, seed, telem, diff, who);
-}
-
-std::vector<torch::Tensor> xbar_linear_entry(
-    const torch::Tensor& x, const torch::Tensor& wq, const torch::Tensor& wraw,
-    const torch::Tensor& bias, int64_t sigma_mode, const torch::Tensor& factor,
-    int64_t xbar_rows, int64_t adc_bits, const torch::Tensor& adc,
-    int64_t seed, bool telem, bool diff, const char* who) {
-  TORCH_CHECK(wq.dim() == 2 && wq.size(1) == x.size(1), who,
-              ": weight shape mismatch");
-  auto g = linear_geom(x, wq.size(0));
-  auto out = torch::empty({x.size(0), wq.size(0)}, x.options());
-  return xbar_fwd_impl(x, wq, wraw, bias, g, out, sigma_mode, factor,
-                       xbar_rows, adc_bits, adc, seed, telem, diff, who);
-}
-
-// slice count of a bit-serial call, after checking in_bits / dac_bits / dac
-int check_xbar_serial_args(int64_t in_bits, int64_t dac_bits,
-                           const torch::Tensor& dac, const torch::Tensor& x,
-                           const char* who) {
-  int64_t top = x.scalar_type() == torch::kBFloat16 ? 7 : 8;
-  TORCH_CHECK(in_bits >= 1 && in_bits <= top, who, ": in_bits must be 1..",
-              top, " for ", x.scalar_type(), " activations (bf16 does not "
-              "carry every 8-bit code), got ", in_bits);
-  TORCH_CHECK(dac_bits >= 1, who, ": dac_bits must be >= 1, got ", dac_bits);
-  int64_t J = (in_bits + dac_bits - 1) / dac_bits;
-  TORCH_CHECK(J <= 4, who, ": in_bits ", in_bits, " at dac_bits ", dac_bits,
-              " is ", J, " slices, at most 4 are built; the smallest "
-              "dac_bits that works is ", (in_bits + 3) / 4);
-  TORCH_CHECK(dac.numel() == 2 && dac.scalar_type() == torch::kFloat32 &&
-                  dac.is_contiguous() && dac.device() == x.device(),
-              who, ": dac must be the fp32 device tensor [x_step, 1/x_step]");
-  return (int)J;
-}
-
-// as xbar_fwd_impl, for xbar_serial_fwd_kernel
-std::vector<torch::Tensor> xbar_serial_fwd_impl(
-    const torch::Tensor& x, torch::Tensor wq2, torch::Tensor wr2,
-    const torch::Tensor& bias, ConvGeom g, torch::Tensor out,
-    int64_t sigma_mode, const torch::Tensor& factor, int64_t xbar_rows,
-    int64_t adc_bits, const torch::Tensor& adc, int64_t in_bits,
-    int64_t dac_bits, const torch::Tensor& dac, int64_t seed, bool telem,
-    const char* who) {
-  check_xbar_args(sigma_mode, xbar_rows, adc_bits, adc, x, who);
-  const int J = check_xbar_serial_args(in_bits, dac_bits, dac, x, who);
-  int nrows = g.R * g.S * g.C;
-  TORCH_CHECK(wq2.dim() == 2 && wq2.size(0) == g.K && wq2.size(1) == nrows &&
-                  wr2.sizes() == wq2.sizes(),
-              who, ": weight shape mismatch");
-  TORCH_CHECK(wq2.scalar_type() == x.scalar_type() &&
-                  wr2.scalar_type() == x.scalar_type(),
-              who, ": x and the weights must share one dtype");
-  int pitch = nrows;
-  if (x.element_size() == 2 && (nrows & 7) != 0) {
-    pitch = (nrows + 7) & ~7;
-    bool same = wr2.is_same(wq2);
-    wq2 = at::constant_pad_nd(wq2, {0, pitch - nrows}, 0);
-    wr2 = same ? wq2 : at::constant_pad_nd(wr2, {0, pitch - nrows}, 0);
-  }
-  wq2 = wq2.contiguous();
-  wr2 = wr2.contiguous();
-  bool has_bias = bias.numel() > 0;
-  if (has_bias) TORCH_CHECK(bias.numel() == g.K, who, ": bias size mismatch");
-  torch::Tensor bias_f;
-  if (has_bias) bias_f = bias.to(torch::kFloat32).contiguous();
-  auto f32 = x.options().dtype(torch::kFloat32);
-  torch::Tensor tele, sat;
-  if (telem) {
-    tele = torch::zeros({5}, f32);
-    tele[2] = -std::numeric_limits<float>::infinity();
-    sat = torch::zeros({1}, x.options().dtype(torch::kLong));
-  } else {
-    tele = torch::empty({0}, f32);
-  }
-  auto factor_f = factor.to(torch::kFloat32).reshape({1}).contiguous();
-  bool adc_on = adc_bits > 0;
-  float qm = adc_on ? (float)((1 << (adc_bits - 1)) - 1) : 0.0f;
-  dim3 grid((g.K + BN - 1) / BN, (int)((g.M + BM - 1) / BM));
-  NN_DISPATCH(x.scalar_type(), "xbar_serial_fwd", [&] {
-    using T = typename DevT<scalar_t>::type;
-    // at most (4 * 64 + 3 * 64) * 144 = 64512 bytes (fp32, four slices)
-    size_t lds = (size_t)(J * BM + 3 * BN) * Mma<T>::STRIDE;
-    auto stream = c10::hip::getCurrentHIPStream();
-    const T* xp = (const T*)x.data_ptr();
-    const T* wqp = (const T*)wq2.data_ptr();
-    const T* wrp = (const T*)wr2.data_ptr();
-    const float* bp = has_bias ? bias_f.data_ptr<float>() : nullptr;
-    T* op = (T*)out.data_ptr();
-    float* tp = telem ? tele.data_ptr<float>() : nullptr;
-    unsigned long long* sp =
-        telem ? (unsigned long long*)sat.data_ptr<int64_t>() : nullptr;
-    const float* f = factor_f.data_ptr<float>();
-    const float* ap = adc_on ? adc.data_ptr<float>() : nullptr;
-    const float* dp = dac.data_ptr<float>();
-    uint64_t sd = (uint64_t)seed;
-    auto launch = [&](auto jj, auto sm, auto ad, auto tl) {
-      hipLaunchKernelGGL((xbar_serial_fwd_kernel<T, decltype(jj)::value,
-                          decltype(sm)::value, decltype(ad)::value,
-                          decltype(tl)::value>), grid, dim3(kBlock), lds,
-                         stream, xp, wqp, wrp, bp, op, g, pitch,
-                         (int)xbar_rows, (int)in_bits, (int)dac_bits, dp, f,
-                         ap, qm, sd, tp, sp, g_seed_base);
-    };
-    using TT = std::true_type; using FF = std::false_type;
-    auto with_telem = [&](auto jj, auto sm, auto ad) {
-      if (telem) launch(jj, sm, ad, TT{}); else launch(jj, sm, ad, FF{});
-    };
-    auto with_adc = [&](auto jj, auto sm) {
-      if (adc_on) with_telem(jj, sm, TT{}); else with_telem(jj, sm, FF{});
-    };
-    auto with_mode = [&](auto jj) {
-      // check_xbar_args left exactly these: 0 (ADC on), 1, 2
-      if (sigma_mode == 0)
-        with_telem(jj, std::integral_constant<int, 0>{}, TT{});
-      else if (sigma_mode == 1) with_adc(jj, std::integral_constant<int, 1>{});
-      else with_adc(jj, std::integral_constant<int, 2>{});
-    };
-    if (J == 1) with_mode(std::integral_constant<int, 1>{});
-    else if (J == 2) with_mode(std::integral_constant<int, 2>{});
-    else if (J == 3) with_mode(std::integral_constant<int, 3>{});
-    else with_mode(std::integral_constant<int, 4>{});
-  });
-  HIP_CHECK_LAST();
-  if (telem) tele.narrow(0, 3, 1).copy_(sat);
-  return {out, tele};
-}
-
-// slice count of a bit-sliced-weight call, after checking w_bits / cell_bits
-// / cell
-int check_xbar_cells_args(int64_t w_bits, int64_t cell_bits,
-                          const torch::Tensor& cell, const torch::Tensor& x,
-                          const char* who) {
-  TORCH_CHECK(cell_bits >= 1 && cell_bits <= 4, who,
-              ": cell_bits must be 1..4, got ", cell_bits);
-  TORCH_CHECK(w_bits >= 1 && w_bits <= 8, who, ": w_bits must be 1..8, got ",
-              w_bits);
-  int64_t slices = (w_bits + cell_bits - 1) / cell_bits;
-  TORCH_CHECK(slices <= 4, who, ": w_bits ", w_bits, " at cell_bits ",
-              cell_bits, " is ", slices, " slices, at most 4 are built; the "
-              "smallest cell_bits that works is ", (w_bits + 3) / 4);
-  TORCH_CHECK(cell.numel() == 3 && cell.scalar_type() == torch::kFloat32 &&
-                  cell.is_contiguous() && cell.device() == x.device(),
-              who, ": cell must be the fp32 device tensor "
-              "[w_step, 1/w_step, w_min]");
-  return (int)slices;
-}
-
-// as xbar_fwd_impl, for xbar_cells_fwd_kernel (no w_raw)
-std::vector<torch::Tensor> xbar_cells_fwd_impl(
-    const torch::Tensor& x, torch::Tensor wq2, const torch::Tensor& bias,
-    ConvGeom g, torch::Tensor out, int64_t sigma_mode,
-    const torch::Tensor& factor, int64_t xbar_rows, int64_t adc_bits,
-    const torch::Tensor& adc, int64_t w_bits, int64_t cell_bits,
-    const torch::Tensor& cell, int64_t seed, bool telem, const char* who,
-    const torch::Tensor* cells = nullptr /* programmed conductances G */) {
-  check_xbar_args(sigma_mode, xbar_rows, adc_bits, adc, x, who);
-  const int NS = check_xbar_cells_args(w_bits, cell_bits, cell, x, who);
-  int nrows = g.R * g.S * g.C;
-  TORCH_CHECK(wq2.dim() == 2 && wq2.size(0) == g.K && wq2.size(1) == nrows,
-              who, ": weight shape mismatch");
-  TORCH_CHECK(wq2.scalar_type() == x.scalar_type(), who,
-              ": x and the weights must share one dtype");
-  int pitch = nrows;
-  const bool prog = cells != nullptr;
-  const bool padded = x.element_size() == 2 && (nrows & 7) != 0;
-  if (padded) pitch = (nrows + 7) & ~7;
-  torch::Tensor gc;
-  if (prog) {
-    // G[T, K, n]: contiguous, or the view xbar_program_cells returns (rows
-    // padded with zeros to a pitch of 8 elements), which is read in place
-    const torch::Tensor& c = *cells;
-    TORCH_CHECK(c.dim() == 3 && c.size(0) == NS && c.size(1) == g.K &&
-                    c.size(2) == nrows,
-                who, ": cells must have the shape [", NS, ", ", g.K, ", ",
-                nrows, "] (slices, output columns, crossbar rows), got ",
-                c.sizes());
-    TORCH_CHECK(c.scalar_type() == x.scalar_type(), who,
-                ": cells must have the dtype of x");
-    TORCH_CHECK(c.device() == x.device(), who,
-                ": cells must be on the device of x");
-    // (the padding must be inside the view's storage: the kernel reads it)
-    const bool pitched =
-        padded && c.stride(2) == 1 && c.stride(1) == pitch &&
-        c.stride(0) == (int64_t)g.K * pitch &&
-        (c.storage_offset() + (int64_t)NS * g.K * pitch) * c.element_size() <=
-            (int64_t)c.storage().nbytes();
-    TORCH_CHECK(c.is_contiguous() || pitched, who,
-                ": cells must be contiguous (or the row-padded view that "
-                "xbar_program_cells returns)");
-    // the 16-bit spans are 16-byte vector loads
-    const bool aligned = ((uintptr_t)c.data_ptr() & 15) == 0;
-    gc = c;
-    if (padded && !(pitched && aligned))
-      gc = at::constant_pad_nd(c, {0, pitch - nrows}, 0).contiguous();
-    else if (!aligned)
-      gc = c.clone();
-  } else {
-    if (padded) wq2 = at::constant_pad_nd(wq2, {0, pitch - nrows}, 0);
-    wq2 = wq2.contiguous();
-  }
-  bool has_bias = bias.numel() > 0;
-  if (has_bias) TORCH_CHECK(bias.numel() == g.K, who, ": bias size mismatch");
-  torch::Tensor bias_f;
-  if (has_bias) bias_f = bias.to(torch::kFloat32).contiguous();
-  auto f32 = x.options().dtype(torch::kFloat32);
-  torch::Tensor tele, sat;
-  if (telem) {
-    tele = torch::zeros({5}, f32);
-    tele[2] = -std::numeric_limits<float>::infinity();
-    sat = torch::zeros({1}, x.options().dtype(torch::kLong));
-  } else {
-    tele = torch::empty({0}, f32);
-  }
-  auto factor_f = factor.to(torch::kFloat32).reshape({1}).contiguous();
-  bool adc_on = adc_bits > 0;
-  float qu = adc_on ? (float)((1 << adc_bits) - 1) : 0.0f;   // unipolar
-  // one-bit digits are their own squares: abs2 runs on the abs instantiation
-  // (not on programmed cells: G^2 != G)
-  const int fold = (sigma_mode == 2 && cell_bits == 1 && !prog) ? 1 : 0;
-  const int64_t kmode = fold ? 1 : sigma_mode;
-  dim3 grid((g.K + BN - 1) / BN, (int)((g.M + BM - 1) / BM));
-  NN_DISPATCH(x.scalar_type(), "xbar_cells_fwd", [&] {
-    using T = typename DevT<scalar_t>::type;
-    // x tile + NS digit tiles (+ NS tiles of squares with abs2): at most
-    // (64 + 8 * 64) * 80 = 46080 bytes for the 16-bit dtypes; fp32 with
-    // four slices and abs2 is 82944 bytes and opts in to the large LDS
-    size_t lds = (size_t)(BM + (kmode == 2 ? 2 : 1) * NS * BN)
-        * Mma<T>::STRIDE;
-    auto stream = c10::hip::getCurrentHIPStream();
-    const T* xp = (const T*)x.data_ptr();
-    const T* wqp = (const T*)wq2.data_ptr();
-    const float* bp = has_bias ? bias_f.data_ptr<float>() : nullptr;
-    T* op = (T*)out.data_ptr();
-    float* tp = telem ? tele.data_ptr<float>() : nullptr;
-    unsigned long long* sp =
-        telem ? (unsigned long long*)sat.data_ptr<int64_t>() : nullptr;
-    const float* f = factor_f.data_ptr<float>();
-    const float* ap = adc_on ? adc.data_ptr<float>() : nullptr;
-    const float* cp = cell.data_ptr<float>();
-    const T* gp = prog ? (const T*)gc.data_ptr() : nullptr;
-    const int64_t gstride = (int64_t)g.K * pitch;
-    uint64_t sd = (uint64_t)seed;
-    auto launch_pg = [&](auto ns, auto sm, auto ad, auto tl, auto pg) {
-      auto kfn = xbar_cells_fwd_kernel<T, decltype(ns)::value,
-                                       decltype(sm)::value,
-                                       decltype(ad)::value,
-                                       decltype(tl)::value,
-                                       decltype(pg)::value>;
-      if (lds > 65536)
-        TORCH_CHECK(hipFuncSetAttribute(
-                        (const void*)kfn,
-                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)lds) == hipSuccess,
-                    who, ": ", lds, " bytes of LDS are not available");
-      hipLaunchKernelGGL(kfn, grid, dim3(kBlock), lds, stream, xp, wqp, bp,
-                         op, g, pitch, (int)xbar_rows, (int)w_bits,
-                         (int)cell_bits, fold, cp, f, ap, qu, sd, tp, sp,
-                         g_seed_base, gp, gstride);
-    };
-    using TT = std::true_type; using FF = std::false_type;
-    auto launch = [&](auto ns, auto sm, auto ad, auto tl) {
-      if (prog) launch_pg(ns, sm, ad, tl, TT{});
-      else launch_pg(ns, sm, ad, tl, FF{});
-    };
-    auto with_telem = [&](auto ns, auto sm, auto ad) {
-      if (telem) launch(ns, sm, ad, TT{}); else launch(ns, sm, ad, FF{});
-    };
-    auto with_adc = [&](auto ns, auto sm) {
-      if (adc_on) with_telem(ns, sm, TT{}); else with_telem(ns, sm, FF{});
-    };
-    auto with_mode = [&](auto ns) {
-      // check_xbar_args left exactly these: 0 (ADC on), 1, 2
-      if (kmode == 0)
-        with_telem(ns, std::integral_constant<int, 0>{}, TT{});
-      else if (kmode == 1) with_adc(ns, std::integral_constant<int, 1>{});
-      else with_adc(ns, std::integral_constant<int, 2>{});
-    };
-    if (NS == 1) with_mode(std::integral_constant<int, 1>{});
-    else if (NS == 2) with_mode(std::integral_constant<int, 2>{});
-    else if (NS == 3) with_mode(std::integral_constant<int, 3>{});
-    else with_mode(std::integral_constant<int, 4>{});
-  });
-  HIP_CHECK_LAST();
-  if (telem) tele.narrow(0, 3, 1).copy_(sat);
-  return {out, tele};
-}
-
-}  // namespace
-
-// bit-sliced weights (w_bits-bit offset-binary codes on the grid
-// w_min + code * w_step, cell_bits per column); cell = fp32
-// [w_step, 1/w_step, w_min]; adc is [step, 1/step] of the unipolar step
-// adc_max / (2^bits - 1)
-std::vector<torch::Tensor> xbar_cells_fwd_conv(
-    torch::Tensor x, torch::Tensor wq, torch::Tensor bias, int64_t stride,
-    int64_t pad, int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
-    int64_t adc_bits, torch::Tensor adc, int64_t w_bits, int64_t cell_bits,
-    torch::Tensor cell, int64_t seed, bool telem) {
-  const char* who = "xbar_cells_fwd_conv";
-  check_cl(x, "xbar_cells_fwd_conv x");
-  check_cl(wq, "xbar_cells_fwd_conv wq");
-  TORCH_CHECK(wq.size(1) == x.size(1), who, ": channel mismatch");
-  auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
-                     (int)x.size(1), (int)wq.size(0), (int)wq.size(2),
-                     (int)wq.size(3), (int)stride, (int)pad);
-  TORCH_CHECK(g.OH > 0 && g.OW > 0, who, ": empty output");
-  auto out = torch::empty({g.N, g.K, g.OH, g.OW},
-                          x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  int64_t nrows = (int64_t)g.R * g.S * g.C;
-  auto wq2 = wq.permute({0, 2, 3, 1}).reshape({(int64_t)g.K, nrows});
-  return xbar_cells_fwd_impl(x, wq2, bias, g, out, sigma_mode, factor,
-                             xbar_rows, adc_bits, adc, w_bits, cell_bits,
-                             cell, seed, telem, who);
-}
-
-std::vector<torch::Tensor> xbar_cells_fwd_linear(
-    torch::Tensor x, torch::Tensor wq, torch::Tensor bias, int64_t sigma_mode,
-    torch::Tensor factor, int64_t xbar_rows, int64_t adc_bits,
-    torch::Tensor adc, int64_t w_bits, int64_t cell_bits, torch::Tensor cell,
-    int64_t seed, bool telem) {
-  const char* who = "xbar_cells_fwd_linear";
-  TORCH_CHECK(wq.dim() == 2 && wq.size(1) == x.size(1), who,
-              ": weight shape mismatch");
-  auto g = linear_geom(x, wq.size(0));
-  auto out = torch::empty({x.size(0), wq.size(0)}, x.options());
-  return xbar_cells_fwd_impl(x, wq, bias, g, out, sigma_mode, factor,
-                             xbar_rows, adc_bits, adc, w_bits, cell_bits,
-                             cell, seed, telem, who);
-}
-
-// the same on programmed cells: ``cells`` = G[T, K, n] of
-// xbar_program_cells (digit units, the dtype of x) stands in for the digits;
-// wq gives the geometry only
-std::vector<torch::Tensor> xbar_prog_fwd_conv(
-    torch::Tensor x, torch::Tensor wq, torch::Tensor cells, torch::Tensor bias,
-    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
-    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t w_bits,
-    int64_t cell_bits, torch::Tensor cell, int64_t seed, bool telem) {
-  const char* who = "xbar_prog_fwd_conv";
-  check_cl(x, "xbar_prog_fwd_conv x");
-  check_cl(wq, "xbar_prog_fwd_conv wq");
-  TORCH_CHECK(wq.size(1) == x.size(1), who, ": channel mismatch");
-  auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
-                     (int)x.size(1), (int)wq.size(0), (int)wq.size(2),
-                     (int)wq.size(3), (int)stride, (int)pad);
-  TORCH_CHECK(g.OH > 0 && g.OW > 0, who, ": empty output");
-  auto out = torch::empty({g.N, g.K, g.OH, g.OW},
-                          x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  int64_t nrows = (int64_t)g.R * g.S * g.C;
-  auto wq2 = wq.permute({0, 2, 3, 1}).reshape({(int64_t)g.K, nrows});
-  return xbar_cells_fwd_impl(x, wq2, bias, g, out, sigma_mode, factor,
-                             xbar_rows, adc_bits, adc, w_bits, cell_bits,
-                             cell, seed, telem, who, &cells);
-}
-
-std::vector<torch::Tensor> xbar_prog_fwd_linear(
-    torch::Tensor x, torch::Tensor wq, torch::Tensor cells, torch::Tensor bias,
-    int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
-    int64_t adc_bits, torch::Tensor adc, int64_t w_bits, int64_t cell_bits,
-    torch::Tensor cell, int64_t seed, bool telem) {
-  const char* who = "xbar_prog_fwd_linear";
-  TORCH_CHECK(wq.dim() == 2 && wq.size(1) == x.size(1), who,
-              ": weight shape mismatch");
-  auto g = linear_geom(x, wq.size(0));
-  auto out = torch::empty({x.size(0), wq.size(0)}, x.options());
-  return xbar_cells_fwd_impl(x, wq, bias, g, out, sigma_mode, factor,
-                             xbar_rows, adc_bits, adc, w_bits, cell_bits,
-                             cell, seed, telem, who, &cells);
-}
-
-// program a layer's weight codes onto imperfect cells (see
-// xbar_program_cells_kernel): wq is a channels-last conv filter [K, C, R, S]
-// (rows in the (r, s, c) order of xbar_cells_fwd_conv) or a linear weight
-// [K, n]. Returns G[T, K, n]; for the 16-bit dtypes the rows sit at a pitch
-// padded to 8 elements and the result is that view.
-torch::Tensor xbar_program_cells(torch::Tensor wq, int64_t w_bits,
-                                 int64_t cell_bits, torch::Tensor cell,
-                                 double sigma, double p_stuck_off,
-                                 double p_stuck_on, int64_t seed, bool fresh) {
-  const char* who = "xbar_program_cells";
-  TORCH_CHECK(wq.is_cuda(), who, ": wq must be a GPU tensor");
-  const int NS = check_xbar_cells_args(w_bits, cell_bits, cell, wq, who);
-  TORCH_CHECK(sigma >= 0.0, who, ": sigma must be >= 0, got ", sigma);
-  TORCH_CHECK(p_stuck_off >= 0.0, who, ": p_stuck_off must be >= 0, got ",
-              p_stuck_off);
-  TORCH_CHECK(p_stuck_on >= 0.0, who, ": p_stuck_on must be >= 0, got ",
-              p_stuck_on);
-  TORCH_CHECK(p_stuck_off + p_stuck_on <= 1.0, who,
-              ": p_stuck_off + p_stuck_on must be <= 1, got ",
-              p_stuck_off + p_stuck_on);
-  TORCH_CHECK(wq.dim() == 2 || wq.dim() == 4, who,
-              ": wq must be a [K, n] or a [K, C, R, S] tensor");
-  torch::Tensor wq2;
-  if (wq.dim() == 4) {
-    check_cl(wq, "xbar_program_cells wq");
-    wq2 = wq.permute({0, 2, 3, 1}).reshape({wq.size(0), -1}).contiguous();
-  } else {
-    wq2 = wq.contiguous();
-  }
-  const int64_t K = wq2.size(0), n = wq2.size(1);
-  TORCH_CHECK(K > 0 && n > 0 && (int64_t)NS * K * (n + 7) < (1ll << 31), who,
-              ": wq is empty or too large");
-  int64_t pitch = n;
-  if (wq2.element_size() == 2 && (n & 7) != 0) pitch = (n + 7) & ~(int64_t)7;
-  auto G = torch::empty({(int64_t)NS, K, pitch}, wq2.options());
-  const int64_t total = K * pitch;
-  NN_DISPATCH(wq2.scalar_type(), "xbar_program_cells", [&] {
-    using T = typename DevT<scalar_t>::type;
-    auto stream = c10::hip::getCurrentHIPStream();
-    hipLaunchKernelGGL(xbar_program_cells_kernel<T>,
-                       dim3((unsigned)((total + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, stream, (const T*)wq2.data_ptr(),
-                       (T*)G.data_ptr(), (int)K, (int)n, (int)pitch, NS,
-                       (int)w_bits, (int)cell_bits, cell.data_ptr<float>(),
-                       (float)sigma, (float)p_stuck_off, (float)p_stuck_on,
-                       (uint64_t)seed, fresh ? 1 : 0, g_seed_base);
-  });
-  HIP_CHECK_LAST();
-  return pitch == n ? G : G.narrow(2, 0, n);
-}
-
-// bit-serial inputs (in_bits-bit codes on the grid x_step, dac_bits per
-// slice); dac = fp32 [x_step, 1/x_step]
-std::vector<torch::Tensor> xbar_serial_fwd_conv(
-    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
-    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
-    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t in_bits,
-    int64_t dac_bits, torch::Tensor dac, int64_t seed, bool telem) {
-  const char* who = "xbar_serial_fwd_conv";
-  check_cl(x, "xbar_serial_fwd_conv x");
-  check_cl(wq, "xbar_serial_fwd_conv wq");
-  check_cl(wraw, "xbar_serial_fwd_conv wraw");
-  TORCH_CHECK(wq.size(1) == x.size(1), who, ": channel mismatch");
-  auto g = make_geom((int)x.size(0), (int)x.size(2), (int)x.size(3),
-                     (int)x.size(1), (int)wq.size(0), (int)wq.size(2),
-                     (int)wq.size(3), (int)stride, (int)pad);
-  TORCH_CHECK(g.OH > 0 && g.OW > 0, who, ": empty output");
-  auto out = torch::empty({g.N, g.K, g.OH, g.OW},
-                          x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  int64_t nrows = (int64_t)g.R * g.S * g.C;
-  auto rows = [&](const torch::Tensor& w) {
-    return w.permute({0, 2, 3, 1}).reshape({(int64_t)g.K, nrows});
-  };
-  auto wq2 = rows(wq);
-  auto wr2 = wraw.is_same(wq) ? wq2 : rows(wraw);
-  return xbar_serial_fwd_impl(x, wq2, wr2, bias, g, out, sigma_mode, factor,
-                              xbar_rows, adc_bits, adc, in_bits, dac_bits,
-                              dac, seed, telem, who);
-}
-
-std::vector<torch::Tensor> xbar_serial_fwd_linear(
-    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
-    int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
-    int64_t adc_bits, torch::Tensor adc, int64_t in_bits, int64_t dac_bits,
-    torch::Tensor dac, int64_t seed, bool telem) {
-  const char* who = "xbar_serial_fwd_linear";
-  TORCH_CHECK(wq.dim() == 2 && wq.size(1) == x.size(1), who,
-              ": weight shape mismatch");
-  auto g = linear_geom(x, wq.size(0));
-  auto out = torch::empty({x.size(0), wq.size(0)}, x.options());
-  return xbar_serial_fwd_impl(x, wq, wraw, bias, g, out, sigma_mode, factor,
-                              xbar_rows, adc_bits, adc, in_bits, dac_bits,
-                              dac, seed, telem, who);
-}
-
-std::vector<torch::Tensor> xbar_fwd_conv(
-    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
-    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
-    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t seed,
-    bool telem) {
-  return xbar_conv_entry(x, wq, wraw, bias, stride, pad, sigma_mode, factor,
-                         xbar_rows, adc_bits, adc, seed, telem, false,
-                         "xbar_fwd_conv");
-}
-
-std::vector<torch::Tensor> xbar_fwd_linear(
-    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
-    int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
-    int64_t adc_bits, torch::Tensor adc, int64_t seed, bool telem) {
-  return xbar_linear_entry(x, wq, wraw, bias, sigma_mode, factor, xbar_rows,
-                           adc_bits, adc, seed, telem, false,
-                           "xbar_fwd_linear");
-}
-
-// differential columns (W+ / W- with unipolar per-column ADCs): same
-// arguments; adc is [step, 1/step] of the unipolar step adc_max / (2^bits - 1)
-std::vector<torch::Tensor> xbar_diff_fwd_conv(
-    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
-    int64_t stride, int64_t pad, int64_t sigma_mode, torch::Tensor factor,
-    int64_t xbar_rows, int64_t adc_bits, torch::Tensor adc, int64_t seed,
-    bool telem) {
-  return xbar_conv_entry(x, wq, wraw, bias, stride, pad, sigma_mode, factor,
-                         xbar_rows, adc_bits, adc, seed, telem, true,
-                         "xbar_diff_fwd_conv");
-}
-
-std::vector<torch::Tensor> xbar_diff_fwd_linear(
-    torch::Tensor x, torch::Tensor wq, torch::Tensor wraw, torch::Tensor bias,
-    int64_t sigma_mode, torch::Tensor factor, int64_t xbar_rows,
-    int64_t adc_bits, torch::Tensor adc, int64_t seed, bool telem) {
-  return xbar_linear_entry(x, wq, wraw, bias, sigma_mode, factor, xbar_rows,
-                           adc_bits, adc, seed, telem, true,
-                           "xbar_diff_fwd_linear");
 }

@@ -845,12 +845,13 @@ def _xbar_publish(telemetry_out, tele, x, y, sigma_mode, current,
 
 class _XbarNoisyConv(torch.autograd.Function):
     """Tiled-crossbar conv: per-block noise + ADC fused into one MFMA pass
-    (xbar_fwd_kernel, csrc/conv_mfma.hip). Backward is the identity straight-through over the
-    noise and the ADC: exactly the gradients of the unblocked conv with wq.
-    A clipped STE would need per-block saturation masks and is not built.
-    ``differential`` selects xbar_diff_fwd_kernel (W+ / W- columns, unipolar
-    ADCs), ``dac_bits`` > 0 xbar_serial_fwd_kernel (bit-serial inputs),
-    ``cell_bits`` > 0 xbar_cells_fwd_kernel (bit-sliced weights; with
+    (xbar_fwd_kernel, csrc/xbar_fwd.hip). Backward is the identity
+    straight-through over the noise and the ADC: exactly the gradients of the
+    unblocked conv with wq. A clipped STE would need per-block saturation
+    masks and is not built. ``differential`` selects xbar_diff_fwd_kernel
+    (W+ / W- columns, unipolar ADCs), ``dac_bits`` > 0 xbar_serial_fwd_kernel
+    (bit-serial inputs, csrc/xbar_serial.hip), ``cell_bits`` > 0
+    xbar_cells_fwd_kernel (bit-sliced weights, csrc/xbar_cells.hip; with
     ``cells`` its programmed path, which reads the conductances G of
     xbar_program_cells in place of the digits); the backward is the same."""
 

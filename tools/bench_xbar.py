@@ -48,7 +48,8 @@ the variants alternating over --rounds rounds in one process; the median
 round is reported. Prints one JSON line per (layer, xbar_rows). There is no
 CPU fallback: a time is a GPU time or it is not reported.
 
---resource-usage needs no GPU: it compiles csrc/conv_mfma.hip for gfx950 with
+--resource-usage needs no GPU: it compiles csrc/xbar_fwd.hip,
+csrc/xbar_serial.hip and csrc/xbar_cells.hip for gfx950 with
 -Rpass-analysis=kernel-resource-usage and prints VGPRs, LDS and scratch of
 every xbar_fwd_kernel, xbar_diff_fwd_kernel, xbar_serial_fwd_kernel and
 xbar_cells_fwd_kernel instantiation (the programmed-cell ones, PROG, listed
@@ -62,6 +63,7 @@ import re
 import statistics
 import subprocess
 import sys
+import tempfile
 
 import torch
 
@@ -70,6 +72,8 @@ sys.path.insert(0, REPO)
 
 from noisynet_amd import ops  # noqa: E402
 from noisynet_amd.ops import reference as ref  # noqa: E402
+
+XBAR_SOURCES = ('xbar_fwd.hip', 'xbar_serial.hip', 'xbar_cells.hip')
 
 LAYERS = {
     'conv2': dict(kind='conv', x=(2048, 65, 14, 14), w=(120, 65, 5, 5)),
@@ -571,17 +575,29 @@ def resource_usage():
     (device-only compile for gfx950, no GPU needed)."""
     from torch.utils import cpp_extension as ce
     import sysconfig
-    src = os.path.join(REPO, 'csrc', 'conv_mfma.hip')
     inc = ['-I' + p for p in ce.include_paths(device_type='cuda')]
     inc.append('-I' + sysconfig.get_paths()['include'])
-    cmd = ['hipcc', '-c', src, '-o', os.devnull, '-O3', '-std=c++17',
-           '--offload-arch=gfx950', '--offload-device-only',
-           '-D__HIP_PLATFORM_AMD__=1', '-DUSE_ROCM=1', '-DTORCH_HIP=1',
-           '-DTORCH_EXTENSION_NAME=noisynet_hip', '-fno-gpu-rdc',
-           '-mllvm', '--amdgpu-mfma-vgpr-form', '-x', 'hip',
-           '-Rpass-analysis=kernel-resource-usage'] + inc
-    text = subprocess.run(cmd, stderr=subprocess.PIPE, text=True,
-                          check=True).stderr
+    # side by side (each takes minutes); the remarks go to files, since a
+    # pipe that nobody reads yet would stall its compiler once it is full
+    procs = []
+    for name in XBAR_SOURCES:
+        cmd = ['hipcc', '-c', os.path.join(REPO, 'csrc', name), '-o',
+               os.devnull, '-O3', '-std=c++17',
+               '--offload-arch=gfx950', '--offload-device-only',
+               '-D__HIP_PLATFORM_AMD__=1', '-DUSE_ROCM=1', '-DTORCH_HIP=1',
+               '-DTORCH_EXTENSION_NAME=noisynet_hip', '-fno-gpu-rdc',
+               '-mllvm', '--amdgpu-mfma-vgpr-form', '-x', 'hip',
+               '-Rpass-analysis=kernel-resource-usage'] + inc
+        err = tempfile.TemporaryFile(mode='w+')
+        procs.append((cmd, subprocess.Popen(cmd, stderr=err), err))
+    text = ''
+    for cmd, p, err in procs:
+        rc = p.wait()
+        err.seek(0)
+        text += err.read()
+        err.close()
+        if rc != 0:
+            raise subprocess.CalledProcessError(rc, cmd)
     return parse_resource_usage(text)
 
 
